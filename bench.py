@@ -20,15 +20,23 @@ Default (N=1) workload — the configuration the metric is quoted on:
   rows, then the fused DeepFM kernel) is nested as `config5` (at N=1:
   `config5_n1`).
 
-Also measured (nested in the JSON line, not `value`):
+A plain N = 1 run sets up, warms up, times the --steps steps, writes the last
+timed step's logits if --dump-outputs DIR is given (DIR/logit.npy; the inputs
+are seeded, so equal arguments give equal inputs) and prints the line: `value`,
+`ms_per_step` and the `roofline` of those same steps.  Everything below that
+takes runs of its own (the eager launch events, `deepfm_forward`,
+`cpu_baseline`, the concurrent / streamed / Zipf legs, configs 3 - 5, the
+empty-kernel slot) is measured only with --full.
+
+Measured beside `value` (nested in the JSON line):
   * `roofline`: the fused gather+FM kernel's algorithmic bytes per launch
     (1,824 B/sample x 4096 + 18.9 KB of parameters) / its
     average launch duration from HIP events recorded around every timed launch
     on the launch stream; peak 8.0 TB/s.  `traffic` = PMC HBM bytes per launch
     from profiles/  or null.
-  * `deepfm_forward`: the full DeepFM forward as ONE kernel (gather + FM +
-    DNN 429-256-128-64-1 on fp32 MFMA + sigmoid head) samples/s.
-  * `cpu_baseline`: the oracle's numpy fp32 restatement of the reference
+  * `deepfm_forward` (--full): the full DeepFM forward as ONE kernel (gather +
+    FM + DNN 429-256-128-64-1 on fp32 MFMA + sigmoid head) samples/s.
+  * `cpu_baseline` (--full): the oracle's numpy fp32 restatement of the reference
     forward (TF unavailable) on the same table and batches, bounded sample.
 
 Other configs (own JSON line): --config deepfm1e6 | dcn | din | pnn | nfm | afm | ffm | io | fm_train.
@@ -319,6 +327,17 @@ def _pool(B, vocabs, nd, n_pool, device, dtype=torch.int32):
     return ids, dense
 
 
+def _dump_outputs(path, tensors):
+    """--dump-outputs: what the timed path left in its output buffers after
+    its last timed step, one ``<name>.npy`` (float32) per buffer.  The inputs
+    are seeded (SEED), so two builds run with the same arguments are compared
+    output for output."""
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def _cpu_threads():
     try:
         from threadpoolctl import threadpool_info
@@ -429,8 +448,11 @@ def bench_hotpath(args, world, rank):
 
         # value: the K timed steps replayed from HIP graphs (no host launch cost)
         dt, slot_ms = _timed_graph(step, args.steps, args.warmup, world)
+        if args.dump_outputs:
+            # the last timed step's logits, before any other leg writes the buffer
+            _dump_outputs(args.dump_outputs, {"logit": logit})
         # kernel duration: HIP events around each launch on the launch stream
-        _, ms = _timed(step, args.steps, 0, world)
+        ms = _timed(step, args.steps, 0, world)[1] if args.full else None
         assert int(err.item()) == 0
         kern_ms = slot_ms  # HIP events over the graph-replayed timed region, per launch
         bytes_per_launch = B * (F * 4 + nd * 4 + F * k * 4 + 4) + prep.numel() * 4
@@ -450,11 +472,16 @@ def bench_hotpath(args, world, rank):
                               "kernel": "embed_fm_mfma_ka", "kernel_ms": kern_ms,
                               "kernel_ms_source": "HIP events around the graph-replayed timed region / steps "
                                                   "(kernel + back-to-back dispatch boundary)",
-                              "eager_launch_event_ms_median": float(np.median(ms)),
+                              "eager_launch_event_ms_median": float(np.median(ms)) if ms is not None else None,
                               "algorithmic_bytes_per_launch": alg_bytes,
                               "bytes_incl_packed_weights": int(bytes_per_launch),
                               "random_64B_row_ceiling_GBps": 3310.0,
                               "frac_of_random_row_ceiling": achieved / 3.31e12}
+        if not args.full:
+            # a plain run stops at the headline figure; every leg below takes
+            # runs of its own and is measured under --full
+            result["cpu_baseline"] = None
+            return result
         # independent batches on parallel streams of one graph (secondary; the
         # headline value above is strictly sequential).  Each stream gets its
         # own output buffer.
@@ -2014,7 +2041,18 @@ def main():
                     help="skip the nested config-3 / config-4 lines of the N = 1 line")
     ap.add_argument("--sharded", action="store_true",
                     help="time the N > 1 line's row-sharded protocol even at world 1 (RCCL self-exchange)")
+    ap.add_argument("--full", action="store_true",
+                    help="the default N = 1 line: also measure everything beside the headline value (eager launch "
+                         "events, concurrent / streamed / Zipf legs, the DeepFM forward, cpu_baseline, configs 3 - 5, "
+                         "the empty-kernel slot); without it the run only times the --steps headline steps")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="the default N = 1 line: after the timed steps write the last timed step's logits to "
+                         "DIR/logit.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.config not in ("hotpath", "deepfm1e6") or args.sharded
+                              or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise SystemExit("--dump-outputs: only the default single-GPU workload (and --config deepfm1e6) writes "
+                         "its outputs")
     _host_wait_mode(os.environ.get("RS_BENCH_SYNC", "spin"))
     world, rank = _dist_setup(args)
     if os.environ.get("RS_PEER_FENCES"):  # A/B of the peer exchange's ordering (rs_option RS_OPT_PEER_FENCES)
@@ -2033,7 +2071,9 @@ def main():
     elif args.config != "hotpath":
         raise SystemExit(f"unknown --config {args.config}")
     dev_state = {"before": _device_state()}
-    empty_slot = _empty_kernel_slot(world)
+    # the sharded / N > 1 lines measure what they always did; --full widens the plain N = 1 line only
+    lean = world == 1 and not args.sharded and not args.full
+    empty_slot = None if lean else _empty_kernel_slot(world)
     res = bench_hotpath(args, world, rank)
     dev_state["after"] = _device_state()
     if rank == 0:

@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py N = 1 line (the nested legs' headline numbers)."""
+"""One-screen summary of a bench.py --full N = 1 line (the nested legs' headline numbers)."""
 import json
 import sys
 

@@ -1,4 +1,4 @@
-"""Turn a gpu_check.sh session (gpurun_out/) into committed summaries under
+"""Turn a gpu_check.sh session (its $OUT folder, check_out/) into committed summaries under
 profiles/ (tag = round, e.g. r1):
 
   profiles/<tag>_rocprof_kernel_stats.csv   rocprofv3 --kernel-trace --stats of bench.py
@@ -22,7 +22,7 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.environ.get("OUT") or os.path.join(ROOT, "check_out")
 P = os.path.join(ROOT, "profiles")
 
 

@@ -10,7 +10,7 @@
         (dense 13 + the 26 one-hot column indices) and the one-hot width
      features_dict(...)                -> the 26 feat_onehot_dim values
    This pins recommender_system_amd.dataset (a2) against the reference itself.
-3. golden_layers.npz / golden_models.npz — fp64 oracle outputs (the
+3. golden_layers.part<N>.npz / golden_models.part<N>.npz — fp64 oracle outputs (the
    restatement of the TF graph; parity unpinned by the reference, which has no
    tests and whose TF is not installed) on seeded inputs/weights, incl. FM and
    DeepFM on the bundled sample (config 1).  They freeze the oracle and give
@@ -18,6 +18,7 @@
 
 Nothing here is shipped to the GPU box except the .npz/.gz data it writes.
 """
+import glob
 import gzip
 import os
 import shutil
@@ -137,14 +138,42 @@ def model_fixtures(rng, ref):
     return g
 
 
+PART_BYTES = 900 * 1024  # raw array bytes per part (random weights do not compress): every file stays under 1 MiB
+
+
+def save_parts(stem, arrays):
+    """Write `arrays` as <stem>.part<N>.npz files of at most PART_BYTES of
+    array data each; an array larger than that goes in as row blocks
+    '<key>@<i>'.  tests/helpers.py load_golden joins the parts again."""
+    blocks = []
+    for key, a in arrays.items():
+        a = np.asarray(a)
+        if a.nbytes <= PART_BYTES:
+            blocks.append((key, a))
+            continue
+        rows = max(1, PART_BYTES // (a.nbytes // a.shape[0]))
+        blocks += [(f"{key}@{i}", a[r:r + rows]) for i, r in enumerate(range(0, a.shape[0], rows))]
+    parts, size = [{}], 0
+    for key, a in blocks:
+        if parts[-1] and size + a.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][key] = a
+        size += a.nbytes
+    for old in glob.glob(stem + ".part*.npz"):
+        os.remove(old)
+    for n, part in enumerate(parts):
+        np.savez_compressed(f"{stem}.part{n}.npz", **part)
+
+
 def main():
     with open(SAMPLE, "rb") as f, gzip.open(os.path.join(HERE, "criteo_train_1w.txt.gz"), "wb", 9) as g:
         shutil.copyfileobj(f, g)
     ref = reference_dataset_fixture()
     np.savez_compressed(os.path.join(HERE, "criteo_ref.npz"), **ref)
     rng = np.random.default_rng(20261015)
-    np.savez_compressed(os.path.join(HERE, "golden_layers.npz"), **layer_fixtures(rng))
-    np.savez_compressed(os.path.join(HERE, "golden_models.npz"), **model_fixtures(rng, ref))
+    save_parts(os.path.join(HERE, "golden_layers"), layer_fixtures(rng))
+    save_parts(os.path.join(HERE, "golden_models"), model_fixtures(rng, ref))
     for n in os.listdir(HERE):
         print(n, os.path.getsize(os.path.join(HERE, n)))
 

@@ -5,9 +5,33 @@ Tolerance contract, fp32 kernels vs the fp64 oracle:
   * logits / intermediates:       |a-b| <= 1e-5 * max(|b|, rms(b))
     (the FM logit cancels: fp32 itself is ~1e-4 relative off near zero).
 """
+import glob
+import os
+
 import numpy as np
 
 RTOL = 1e-5
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def load_golden(stem):
+    """The arrays of tests/golden/<stem>.part<N>.npz as one dict (written by
+    make_golden.py's save_parts, which keeps every committed file under 1 MiB):
+    an array too large for one part is stored as row blocks '<key>@<i>' and
+    joined here in order."""
+    out, blocks = {}, {}
+    for path in sorted(glob.glob(os.path.join(GOLDEN, stem + ".part*.npz"))):
+        with np.load(path) as z:
+            for key in z.files:
+                if "@" in key:
+                    name, i = key.split("@")
+                    blocks.setdefault(name, {})[int(i)] = z[key]
+                else:
+                    out[key] = z[key]
+    assert out or blocks, f"no tests/golden/{stem}.part*.npz"
+    for name, b in blocks.items():
+        out[name] = np.concatenate([b[i] for i in range(len(b))])
+    return out
 
 
 def _np(x):
