@@ -338,7 +338,7 @@ int rs_embed_inner_fwd_hm(const void* ids, int id_kind, int64_t id_stride,
  * sum_{a,j} e[b,row_p,j] W[a,p,j] e[b,col_p,a] with W the Keras weight
  * [k, P, k], pairs in the reference's row-major i<j order.  rs_outer_prepare
  * packs W into per-lane MFMA fragments (rs_outer_prepared_size floats; k in
- * {4,8,16,32,64}, 2..64 fields).  rs_outer_product_fwd: emb [B,F,k] -> out
+ * {4,8,16,32,64}, 2..128 fields).  rs_outer_product_fwd: emb [B,F,k] -> out
  * [B,P].  rs_embed_product_fwd: PNN's DNN input (model/pnn.py:32-48) from ids
  * in one launch — out[b] = [flat_emb (F*k) | inner (P, if inner) | outer (P,
  * if outer_prepared)]; mode 'inner' / 'outer' / 'both'.                      */
@@ -363,6 +363,60 @@ int rs_embed_product_fwd_hm(const void* ids, int id_kind, int64_t id_stride,
                             int inner, const float* outer_prepared, float* out,
                             int64_t out_stride, int64_t batch, int* err_flag,
                             rs_stream_t stream);
+/* The same row from a GIVEN emb [B,F,k] in one launch: out[b] = [flat (F*k) |
+ * inner (P, if inner) | outer (P, if outer_prepared)] — PNN's DNN input when
+ * the product layers run on z = concat([embed, fgcnn_out]) (model/pnn.py:
+ * 33-48).  From given embeddings (this entry, rs_inner_product_fwd,
+ * rs_outer_prepare*, rs_outer_product_fwd) the MFMA path takes 2..128 fields;
+ * from ids (rs_embed_*) 2..64.  As many samples per workgroup as fit in 96
+ * KB of LDS (per sample F*k + 4 + pairs floats; the largest shape, 128
+ * fields, k 64, inner and outer, is 97,808 bytes: one sample).  A tile past
+ * that budget would return RS_ERR_ARG and launch nothing.                  */
+int rs_product_fwd(const float* emb, int n_fields, int k, int inner,
+                   const float* outer_prepared, float* out, int64_t out_stride,
+                   int64_t batch, rs_stream_t stream);
+
+/* ---------------------------------------------- FGCNN conv stack (a12)
+ * FGCNNLayer.call (layer/interaction.py:245-258) on e [B, F, k], x = e[...,
+ * None]; layer i = 0..n_layers-1 on its input map [H, k, Cin] (H_0 = F,
+ * Cin_0 = 1):
+ *   Conv2D(filters[i], (kernel_width[i], 1), 'same', tanh): along the field
+ *     axis only, kernel conv_w[i] [kw, 1, Cin, Cout] (Keras shape), bias
+ *     conv_b[i] [Cout]; TF 'same' pads (kw-1)/2 rows before, the rest after;
+ *   MaxPool2D((pooling_width[i], 1)): H' = H / pw, trailing rows dropped.
+ * The pooled map [H', k, Cout] is the next layer's input and is written, in
+ * Keras Flatten order, to workspace[b, off_i : off_i + H'*k*Cout] (off_i = the
+ * sum of the earlier layers' sizes; rows ws_stride floats apart) — the x of
+ * the layer's recombination Dense (rs_dense_fwd with y inside z at the
+ * layer's column offset).  All layers run in ONE launch; the maps stay in LDS.
+ * rs_fgcnn_workspace_size: floats per sample (the sum over layers), or -1 for
+ * a configuration outside 1..4 layers, 1..32 filters, kernel_width >= 1,
+ * pooling_width >= 1, k in {4,8,16,32,64}, every H' >= 1 and the per-sample
+ * LDS tile (padded maps + the staged weights <= 128 KB).
+ * filters / kernel_width / pooling_width: host int[n_layers]; conv_w / conv_b:
+ * host arrays of device pointers.
+ * rs_embed_fgcnn_conv_fwd: the same from ids (gather arguments as
+ * rs_embed_inner_fwd: an out-of-range id reads a zero row and sets
+ * *err_flag); the gathered rows also go to z[b, 0:F*k] (rows z_stride floats
+ * apart; z may be NULL), so PNN needs no separate gather.  Bit-identical to
+ * rs_fgcnn_conv_fwd on the gathered rows.                                   */
+int64_t rs_fgcnn_workspace_size(int n_fields, int k, int n_layers,
+                                const int* filters, const int* kernel_width,
+                                const int* pooling_width);
+int rs_fgcnn_conv_fwd(const float* emb, int n_fields, int k, int n_layers,
+                      const int* filters, const int* kernel_width,
+                      const int* pooling_width, const float* const* conv_w,
+                      const float* const* conv_b, float* workspace,
+                      int64_t ws_stride, int64_t batch, rs_stream_t stream);
+int rs_embed_fgcnn_conv_fwd(const void* ids, int id_kind, int64_t id_stride,
+                            const float* table, const int64_t* field_offsets,
+                            const int64_t* field_vocab, int n_fields, int k,
+                            int n_layers, const int* filters,
+                            const int* kernel_width, const int* pooling_width,
+                            const float* const* conv_w,
+                            const float* const* conv_b, float* workspace,
+                            int64_t ws_stride, float* z, int64_t z_stride,
+                            int64_t batch, int* err_flag, rs_stream_t stream);
 
 /* ---------------------------------------------- DIN attention unit (a13)
  * Attention.call (layer/interaction.py:369-406), 'prelu' mode:

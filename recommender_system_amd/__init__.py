@@ -8,7 +8,7 @@ reference's Keras layer / model names and signatures.
 """
 from . import _lib  # noqa: F401
 from .layers import (AFMLayer, Attention, AttentionLayer, BatchNormalization, CrossLayer, Dense, Dice,  # noqa: F401
-                     DNNLayer, EmbedLayer, FFMLayer, FMLayer, InnerProductLayer, InteractionLayer,
+                     DNNLayer, EmbedLayer, FFMLayer, FGCNNLayer, FMLayer, InnerProductLayer, InteractionLayer,
                      OuterProductLayer, sigmoid_combine)
 from .models import AFM, DCN, DIN, FFM, FM, NFM, PNN, DeepFM  # noqa: F401
 from .dataset import create_criteo_dataset, denseFeature, features_dict, sparseFeature  # noqa: F401

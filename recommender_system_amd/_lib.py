@@ -65,6 +65,10 @@ SIGNATURES = {
     "rs_outer_product_fwd": (I, [P, I, I, P, P, L, L, P]),
     "rs_embed_product_fwd": (I, [P, I, L, P, P, P, I, I, I, P, P, L, L, P, P]),
     "rs_embed_product_fwd_hm": (I, [P, I, L, P, P, P, P, P, I, I, I, P, P, L, L, P, P]),
+    "rs_product_fwd": (I, [P, I, I, I, P, P, L, L, P]),
+    "rs_fgcnn_workspace_size": (L, [I, I, I, P, P, P]),
+    "rs_fgcnn_conv_fwd": (I, [P, I, I, I, P, P, P, P, P, P, L, L, P]),
+    "rs_embed_fgcnn_conv_fwd": (I, [P, I, L, P, P, P, I, I, I, P, P, P, P, P, P, L, P, L, L, P, P]),
     "rs_din_attention_fwd": (I, [P, P, P, P, I, I, P, P, P, I, P, P, P, I, P, P, P, L, P]),
     "rs_din_attention_dice_fwd": (I, [P, P, P, P, I, I, I, P, P, P, F, P, P, P, L, P]),
     "rs_din_prepared_size": (L, [I, I, I, I]),

@@ -17,6 +17,7 @@ namespace rs {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int GBM = 64, GBN = 64, GBK = 16;
+constexpr int GBK_LONG = 4096, GBK_BLOCK = 1024;  // sums longer than GBK_LONG run as blocks of GBK_BLOCK terms
 
 struct DenseArgs {
   const float* x;
@@ -47,6 +48,8 @@ __device__ __forceinline__ float apply_act(float v, int act, float alpha) {
   }
 }
 
+// BLOCKED: see the K loop (sums longer than GBK_LONG); false = one chain, the kernel as it always was
+template <bool BLOCKED>
 __global__ __launch_bounds__(256) void dense_mfma(DenseArgs a) {
   __shared__ float As[2][GBK][GBM + 4];
   __shared__ float Bs[2][GBK][GBN + 4];
@@ -87,8 +90,26 @@ __global__ __launch_bounds__(256) void dense_mfma(DenseArgs a) {
   store_tiles(0);
   __syncthreads();
   const int li = lane & 31, lk = lane >> 5;
+  // K > GBK_LONG: the sum is cut into blocks of GBK_BLOCK terms, each its own
+  // MFMA chain, added in block order (one fp32 chain over ~8,000 terms — PNN's
+  // first tower layer on the 83-field product row — measured 1.0e-5 scaled
+  // error on the logit; blocked sums stay near 1e-6).  Shorter sums are one
+  // chain, as before.
+  constexpr bool blocked = BLOCKED;
+  floatx16 tot;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) tot[r] = 0.f;
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
+    if constexpr (blocked) {
+      if (kt > 0 && kt % (GBK_BLOCK / GBK) == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          tot[r] += acc[r];
+          acc[r] = 0.f;
+        }
+      }
+    }
     if (kt + 1 < nk) load_tiles((kt + 1) * GBK);
 #pragma unroll
     for (int ks = 0; ks < GBK / 2; ++ks) {
@@ -98,6 +119,10 @@ __global__ __launch_bounds__(256) void dense_mfma(DenseArgs a) {
     }
     if (kt + 1 < nk) store_tiles(cur ^ 1);
     __syncthreads();
+  }
+  if constexpr (blocked) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] += tot[r];
   }
   // epilogue: lane holds col = lane&31, rows (r&3) + 8*(r>>2) + 4*(lane>>5)
   const int n = n0 + wn * 32 + li;
@@ -172,7 +197,8 @@ static int dense_launch(const DenseArgs& a, hipStream_t st, const char* what) {
     dense_small_n<<<(unsigned)g, 256, 0, st>>>(a);
   } else {
     dim3 grid((a.N + GBN - 1) / GBN, (unsigned)((a.M + GBM - 1) / GBM));
-    dense_mfma<<<grid, 256, 0, st>>>(a);
+    if (a.K > GBK_LONG) dense_mfma<true><<<grid, 256, 0, st>>>(a);
+    else dense_mfma<false><<<grid, 256, 0, st>>>(a);
   }
   return launch_status(what);
 }

@@ -131,7 +131,9 @@ __global__ __launch_bounds__(256) void inner_kernel(InnerArgs a) {
 }
 
 // ---------------------------------------------------------------- fast path
-// k in {4,8,16,32,64}, F <= 64.  Up to 16 samples per 1024-thread workgroup:
+// k in {4,8,16,32,64}, F <= 64 from ids, F <= 128 from given embeddings (as
+// many samples per workgroup as fit in 96 KB of LDS).  Up to 16 samples per
+// 1024-thread workgroup:
 //  1. the workgroup's S x F ids and the F (offset, vocab) pairs -> LDS
 //     (coalesced, once), barrier;
 //  2. every row chunk (float4) of the S x F x k tile is requested up front
@@ -143,7 +145,8 @@ __global__ __launch_bounds__(256) void inner_kernel(InnerArgs a) {
 //     block of dword stores.
 constexpr int IP_SMAX = 16;
 constexpr int IP_NW = 16, IP_NT = IP_NW * 64;  // 16 waves: one sample per wave in the Gram phase
-constexpr int IP_FMAX = 64;
+constexpr int IP_FMAX = 64;       // ids path: the static id tile lid[IP_SMAX][IP_FMAX]
+constexpr int IP_FMAX_EMB = 128;  // embeddings given (no id tile): bounded by the per-sample LDS tile
 
 // KA (inner_fast_ka, rs_embed_inner_fwd_hm / rs_embed_product_fwd_hm: K = 16,
 // <= 32 fields, 16 samples per workgroup): the rows come in through the
@@ -450,12 +453,14 @@ static void launch_inner_fast_k(const InnerArgs& a, size_t lds, unsigned grid, h
 static int launch_inner(InnerArgs a, hipStream_t st, const char* what, const FieldMeta* hm = nullptr) {
   if (a.batch == 0) return RS_OK;
   const bool fast_k = a.k == 4 || a.k == 8 || a.k == 16 || a.k == 32 || a.k == 64;
-  if (fast_k && a.F >= 2 && a.F <= IP_FMAX) {
+  if (fast_k && a.F >= 2 && a.F <= (a.ids ? IP_FMAX : IP_FMAX_EMB)) {
     const int P = a.F * (a.F - 1) / 2;
     const int PP = (a.want_inner ? P : 0) + (a.outer_img ? P : 0);
     const int64_t per = ((int64_t)a.F * a.k + 4 + PP) * sizeof(float);
     int S = IP_SMAX;
     while (S > 1 && S * per > 96 * 1024) --S;
+    RS_REQUIRE(S * per <= 96 * 1024, "%s: one sample's tile (%d fields, k %d: %lld bytes) does not fit in LDS", what,
+               a.F, a.k, (long long)per);
     a.S = S;
     const int FKw = a.write_flat ? a.F * a.k : 0;
     const int W = FKw + PP;
@@ -465,6 +470,14 @@ static int launch_inner(InnerArgs a, hipStream_t st, const char* what, const Fie
     const size_t lds = (size_t)S * per;
     const unsigned grid = (unsigned)((a.batch + S - 1) / S);
     if (a.ids == nullptr) {
+      if (lds > 64 * 1024) {
+        static LdsAttr set[5];
+        const void* kern[5] = {(const void*)inner_fast<4, 3>, (const void*)inner_fast<8, 3>,
+                               (const void*)inner_fast<16, 3>, (const void*)inner_fast<32, 3>,
+                               (const void*)inner_fast<64, 3>};
+        const int ki = a.k == 4 ? 0 : a.k == 8 ? 1 : a.k == 16 ? 2 : a.k == 32 ? 3 : 4;
+        lds_attr(set[ki], kern[ki], lds);
+      }
       launch_inner_fast_k<3>(a, lds, grid, st);
     } else if (hm && a.k == 16 && a.F <= 32 && S == IP_SMAX) {
       with_id_kind(a.id_kind, [&](auto K) {
@@ -520,13 +533,13 @@ static int64_t outer_size(int F, int k) {
 using namespace rs;
 
 extern "C" int64_t rs_outer_prepared_size(int n_fields, int k) {
-  if (n_fields < 2 || n_fields > IP_FMAX || !(k == 4 || k == 8 || k == 16 || k == 32 || k == 64)) return -1;
+  if (n_fields < 2 || n_fields > IP_FMAX_EMB || !(k == 4 || k == 8 || k == 16 || k == 32 || k == 64)) return -1;
   return outer_size(n_fields, k);
 }
 
 extern "C" int rs_outer_prepare(const float* W, int n_fields, int k, float* prepared, rs_stream_t stream) {
   RS_REQUIRE(rs_outer_prepared_size(n_fields, k) > 0, "rs_outer_prepare: need 2..%d fields, k in {4,8,16,32,64}",
-             IP_FMAX);
+             IP_FMAX_EMB);
   RS_REQUIRE(W && prepared, "rs_outer_prepare: null pointer");
   const int64_t n = outer_size(n_fields, k);
   int64_t g = (n + 255) / 256;
@@ -616,7 +629,7 @@ extern "C" int rs_embed_product_fwd_hm(const void* ids, int id_kind, int64_t id_
   RS_REQUIRE(field_offsets_host && field_vocab_host, "rs_embed_product_fwd_hm: host metadata missing");
   RS_REQUIRE(ids && table && field_offsets && field_vocab && out, "rs_embed_product_fwd_hm: null pointer");
   RS_REQUIRE(inner || outer_prepared, "rs_embed_product_fwd_hm: nothing to compute (inner=0, no outer weights)");
-  RS_REQUIRE(rs_outer_prepared_size(n_fields, k) > 0,
+  RS_REQUIRE(n_fields <= IP_FMAX && rs_outer_prepared_size(n_fields, k) > 0,
              "rs_embed_product_fwd_hm: need 2..%d fields and k in {4,8,16,32,64}", IP_FMAX);
   RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32 && batch >= 0, "rs_embed_product_fwd_hm: bad ids");
   const int P = n_fields * (n_fields - 1) / 2;
@@ -685,7 +698,7 @@ extern "C" int rs_embed_product_fwd(const void* ids, int id_kind, int64_t id_str
   if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
   RS_REQUIRE(ids && table && field_offsets && field_vocab && out, "rs_embed_product_fwd: null pointer");
   RS_REQUIRE(inner || outer_prepared, "rs_embed_product_fwd: nothing to compute (inner=0, no outer weights)");
-  RS_REQUIRE(rs_outer_prepared_size(n_fields, k) > 0,
+  RS_REQUIRE(n_fields <= IP_FMAX && rs_outer_prepared_size(n_fields, k) > 0,
              "rs_embed_product_fwd: need 2..%d fields and k in {4,8,16,32,64}", IP_FMAX);
   RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32 && batch >= 0, "rs_embed_product_fwd: bad ids");
   const int P = n_fields * (n_fields - 1) / 2;
@@ -719,7 +732,7 @@ extern "C" int rs_outer_product_fwd(const float* emb, int n_fields, int k, const
   if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
   RS_REQUIRE(emb && outer_prepared && out, "rs_outer_product_fwd: null pointer");
   RS_REQUIRE(rs_outer_prepared_size(n_fields, k) > 0,
-             "rs_outer_product_fwd: need 2..%d fields and k in {4,8,16,32,64}", IP_FMAX);
+             "rs_outer_product_fwd: need 2..%d fields and k in {4,8,16,32,64}", IP_FMAX_EMB);
   RS_REQUIRE(out_stride >= (int64_t)n_fields * (n_fields - 1) / 2 && batch >= 0,
              "rs_outer_product_fwd: out_stride too small");
   RS_REQUIRE((uintptr_t)emb % 16 == 0, "rs_outer_product_fwd: emb must be 16-B aligned");
@@ -735,4 +748,33 @@ extern "C" int rs_outer_product_fwd(const float* emb, int n_fields, int k, const
   a.outer_off = 0;
   a.batch = batch;
   return launch_inner(a, as_stream(stream), "rs_outer_product_fwd");
+}
+
+// [flat | inner | outer] from given embeddings (model/pnn.py:37-48 on z =
+// concat([embed, fgcnn_out])): the fast path with no ids and the flat copy.
+extern "C" int rs_product_fwd(const float* emb, int n_fields, int k, int inner, const float* outer_prepared,
+                              float* out, int64_t out_stride, int64_t batch, rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  RS_REQUIRE(emb && out, "rs_product_fwd: null pointer");
+  RS_REQUIRE(inner || outer_prepared, "rs_product_fwd: nothing to compute (inner=0, no outer weights)");
+  RS_REQUIRE(rs_outer_prepared_size(n_fields, k) > 0, "rs_product_fwd: need 2..%d fields and k in {4,8,16,32,64}",
+             IP_FMAX_EMB);
+  const int P = n_fields * (n_fields - 1) / 2;
+  RS_REQUIRE(batch >= 0 && out_stride >= (int64_t)n_fields * k + (inner ? P : 0) + (outer_prepared ? P : 0),
+             "rs_product_fwd: out_stride too small");
+  RS_REQUIRE((uintptr_t)emb % 16 == 0, "rs_product_fwd: emb must be 16-B aligned");
+  InnerArgs a{};
+  a.dbg = g_inner_dbg;
+  a.emb = emb;
+  a.F = n_fields;
+  a.k = k;
+  a.out = out;
+  a.out_stride = out_stride;
+  a.write_flat = 1;
+  a.want_inner = inner ? 1 : 0;
+  a.inner_off = n_fields * k;
+  a.outer_img = outer_prepared;
+  a.outer_off = n_fields * k + (inner ? P : 0);
+  a.batch = batch;
+  return launch_inner(a, as_stream(stream), "rs_product_fwd");
 }

@@ -7,6 +7,8 @@ Each class keeps the reference layer's name, constructor arguments and
   FMLayer(k, reg_w=1e-4, reg_b=1e-4)          layer/interaction.py:86-114
   CrossLayer(layer_num, reg_w, reg_b)         layer/interaction.py:49-83
   InnerProductLayer()                         layer/interaction.py:166-183
+  FGCNNLayer(filters, kernel_width, dnn_maps, pooling_width)
+                                              layer/interaction.py:218-258
   DNNLayer(hidden_units, output_dim, activation='relu', dropout=0.2)
                                               layer/interaction.py:30-46
   Attention(hidden_units, activation='prelu') layer/interaction.py:355-406
@@ -405,6 +407,140 @@ class OuterProductLayer(KerasModule):
         call("rs_outer_product_fwd", ptr(e.contiguous()), F, k, ptr(self.prepared()), ptr(out), out.stride(0), B,
              _stream())
         return out
+
+
+class FGCNNLayer(KerasModule):
+    """FGCNNLayer(filters=[14,16], kernel_width=[7,7], dnn_maps=[3,3],
+    pooling_width=[2,2]) — layer/interaction.py:218-258.  Per layer
+    Conv2D(filters, (kernel_width, 1), 'same', tanh) along the field axis,
+    MaxPool2D((pooling_width, 1)), Flatten, Dense(dnn_maps * H' * k, relu),
+    reshaped to [B, dnn_maps * H', k]; the layers' results are concatenated
+    along the field axis.  ``forward(e[B,F,k]) -> [B, n_new, k]``.
+
+    The whole conv stack is ONE launch (rs_fgcnn_conv_fwd, or
+    rs_embed_fgcnn_conv_fwd straight from ids); each recombination Dense is
+    rs_dense_fwd on the launch's workspace.  Deviation: the reference builds
+    the recombination Dense layers inside ``call`` (fresh weights per call);
+    here they are built once (glorot-uniform kernel, zero bias) and exchanged
+    by name: conv_i/kernel [kw, 1, Cin, Cout], conv_i/bias, dense_i/kernel,
+    dense_i/bias."""
+
+    def __init__(self, filters=(14, 16), kernel_width=(7, 7), dnn_maps=(3, 3), pooling_width=(2, 2), device=None,
+                 seed=None):
+        super().__init__(device, seed)
+        self.filters = [int(v) for v in filters]
+        self.kernel_width = [int(v) for v in kernel_width]
+        self.dnn_maps = [int(v) for v in dnn_maps]
+        self.pooling_width = [int(v) for v in pooling_width]
+        n = len(self.filters)
+        if not (len(self.kernel_width) == len(self.dnn_maps) == len(self.pooling_width) == n):
+            raise ValueError("FGCNNLayer: filters, kernel_width, dnn_maps and pooling_width need one entry per layer")
+        if any(m < 1 for m in self.dnn_maps):
+            raise ValueError("FGCNNLayer: dnn_maps must be >= 1")
+        self.conv_kernels = nn.ParameterList()
+        self.conv_biases = nn.ParameterList()
+        self.dense_layers = nn.ModuleList()
+        self.field_num = self.k = None
+
+    @property
+    def built(self):
+        return self.field_num is not None
+
+    def _cfg(self):
+        arr = lambda v: (C.c_int * len(v))(*v)
+        return len(self.filters), arr(self.filters), arr(self.kernel_width), arr(self.pooling_width)
+
+    def build(self, F, k):
+        F, k = int(F), int(k)
+        ws = _lib.lib().rs_fgcnn_workspace_size(F, k, *self._cfg())
+        if ws < 0:
+            _lib.check(-1, "rs_fgcnn_workspace_size")
+        self.ws_size = int(ws)
+        self.pooled_shapes, self.new_fields = [], []  # per layer (H', k, Cout) and dnn_maps * H'
+        H, cin = F, 1
+        for cout, kw, maps, pw in zip(self.filters, self.kernel_width, self.dnn_maps, self.pooling_width):
+            # Keras Conv2D glorot_uniform: fans = receptive field (kw * 1) x channels
+            lim = math.sqrt(6.0 / (kw * cin + kw * cout))
+            w = (torch.rand(kw, 1, cin, cout, generator=self._gen, device="cpu") * 2 - 1).mul_(lim)
+            self.conv_kernels.append(nn.Parameter(w.to(self._dev), requires_grad=False))
+            self.conv_biases.append(nn.Parameter(torch.zeros(cout, device=self._dev), requires_grad=False))
+            H = H // pw
+            self.pooled_shapes.append((H, k, cout))
+            self.new_fields.append(maps * H)
+            self.dense_layers.append(Dense(maps * H * k, "relu", device=self._dev, seed=_subseed(self._gen),
+                                           input_dim=H * k * cout))
+            cin = cout
+        self.n_new = sum(self.new_fields)
+        self.field_num, self.k = F, k
+
+    def keras_weights(self):
+        out = {}
+        for i, (w, b, d) in enumerate(zip(self.conv_kernels, self.conv_biases, self.dense_layers)):
+            out[f"conv_{i}/kernel"], out[f"conv_{i}/bias"] = w, b
+            out[f"dense_{i}/kernel"], out[f"dense_{i}/bias"] = d.kernel, d.bias
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        own = self.keras_weights()
+        if strict and set(own) != set(weights):
+            raise KeyError(f"FGCNNLayer: expected weights {sorted(own)}, got {sorted(weights)}")
+        with torch.no_grad():
+            for name, p in own.items():
+                if name in weights:
+                    p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
+
+    def _weight_ptrs(self):
+        n = len(self.filters)
+        return ((C.c_void_p * n)(*[ptr(w) for w in self.conv_kernels]),
+                (C.c_void_p * n)(*[ptr(b) for b in self.conv_biases]))
+
+    def _check_shape(self, F, k):
+        if not self.built:
+            self.build(F, k)
+        if (F, k) != (self.field_num, self.k):
+            raise ValueError(f"FGCNNLayer built for F={self.field_num}, k={self.k}; got {F}, {k}")
+
+    def conv(self, e, ws=None):
+        """The conv stack on e [B,F,k]: every layer's pooled map, flattened in
+        Keras order, side by side in ws [B, ws_size] (one launch)."""
+        e = _to_device_f32(e, self._dev)
+        B, F, k = e.shape
+        self._check_shape(F, k)
+        if ws is None:
+            ws = torch.empty(B, self.ws_size, dtype=torch.float32, device=self._dev)
+        cw, cb = self._weight_ptrs()
+        call("rs_fgcnn_conv_fwd", ptr(e), F, k, *self._cfg(), cw, cb, ptr(ws), ws.stride(0), B, _stream())
+        return ws
+
+    def conv_ids(self, ids, embed, z, err, ws=None):
+        """The conv stack straight from ids [B,F] through EmbedLayer `embed`;
+        the gathered rows also land in z[:, :F*k] (one launch)."""
+        B = ids.shape[0]
+        self._check_shape(embed.n_fields, embed.k)
+        if ws is None:
+            ws = torch.empty(B, self.ws_size, dtype=torch.float32, device=self._dev)
+        cw, cb = self._weight_ptrs()
+        call("rs_embed_fgcnn_conv_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(embed.table),
+             ptr(embed.field_offsets), ptr(embed.field_vocab), embed.n_fields, embed.k, *self._cfg(), cw, cb, ptr(ws),
+             ws.stride(0), ptr(z), 0 if z is None else z.stride(0), B, ptr(err), _stream())
+        return ws
+
+    def recombine(self, ws, out, col=0):
+        """Dense(dnn_maps * H' * k, relu) of every layer's pooled map, written
+        side by side into out[:, col:col + n_new*k] (one rs_dense_fwd each)."""
+        off = 0
+        for (H, k, cout), d in zip(self.pooled_shapes, self.dense_layers):
+            n = H * k * cout
+            d(ws[:, off:off + n], out=out[:, col:col + d.units])
+            off += n
+            col += d.units
+        return out
+
+    def forward(self, inputs):
+        e = _to_device_f32(inputs, self._dev)
+        ws = self.conv(e)
+        out = torch.empty(e.shape[0], self.n_new * self.k, dtype=torch.float32, device=self._dev)
+        return self.recombine(ws, out).view(e.shape[0], self.n_new, self.k)
 
 
 # -------------------------------------------------------------- dense / MLP

@@ -29,9 +29,11 @@ uses k=8 (layer/core.py:268-271), so 8 is the drop-in behaviour.
 
 PNN runs with 3-D embeddings [B,F,k] (documented deviation: the reference's
 rank-2 EmbedLayer makes PNN.call raise at model/pnn.py:38).  Modes 'inner',
-'outer' and 'both' are built (forward and training); use_fgcnn=True is
-outside this build's hot path and raises NotImplementedError; an unknown mode
-raises the reference's ValueError.
+'outer' and 'both' are built (forward and training); an unknown mode raises
+the reference's ValueError.  use_fgcnn=True (forward only, HIP device only:
+building it for another device raises NotImplementedError) runs the product
+layers and the flat part on z = concat([embed, FGCNNLayer(embed)], axis=1)
+(model/pnn.py:33-48); extra keyword ``fgcnn`` passes FGCNNLayer's arguments.
 """
 from __future__ import annotations
 
@@ -42,7 +44,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr
 from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense, DNNLayer, EmbedLayer, FFMLayer,
-                     FMLayer, InnerProductLayer, OuterProductLayer,
+                     FGCNNLayer, FMLayer, InnerProductLayer, OuterProductLayer,
                      KerasModule, TowerMixin, sigmoid_combine, _ids_tensor, _to_device_f32, _ErrFlag)
 
 
@@ -655,28 +657,41 @@ class PNN(KerasModule):
     embeddings (the reference reshapes them to 2-D before the product layers
     and crashes at :38).  mode 'inner' / 'outer' / 'both'; the DNN input
     [flat_emb | inner | outer] comes out of ONE launch (rs_embed_product_fwd).
-    Returns the DNN logit (no sigmoid, as the reference)."""
+    use_fgcnn=True: the products and the flat part run on z = concat([embed,
+    FGCNNLayer(embed)], axis=1) (model/pnn.py:33-36) — the conv stack from the
+    ids (which also gathers embed into z), one Dense per FGCNN layer into z,
+    then rs_product_fwd on z; ``fgcnn`` (a dict) passes FGCNNLayer's
+    arguments.  Returns the DNN logit (no sigmoid, as the reference)."""
 
     def __init__(self, feature_columns, mode, hidden_units, output_dim, activation="relu", dropout=0.2,
-                 use_fgcnn=False, embed_dim=8, device=None, seed=None):
+                 use_fgcnn=False, embed_dim=8, device=None, seed=None, fgcnn=None):
         super().__init__(device, seed)
         if mode not in ("inner", "outer", "both"):
             raise ValueError("Please choice mode's value in 'inner', 'outer', 'both'.")
-        if use_fgcnn:
-            raise NotImplementedError("PNN use_fgcnn=True: FGCNNLayer is outside this build's hot path")
+        self.use_fgcnn = bool(use_fgcnn)
+        if self.use_fgcnn and self._dev.type != "cuda":
+            # FGCNN exists only as HIP kernels; a model built for another device
+            # could never run it, so it is refused when it is built
+            raise NotImplementedError("PNN use_fgcnn=True: FGCNNLayer runs only on a HIP device "
+                                      f"(device={self._dev})")
         self.mode = mode
         self.dense_feature_columns, self.sparse_feature_columns = feature_columns
         self.nd = len(self.dense_feature_columns)
         self.embed_layer = EmbedLayer(self.sparse_feature_columns, embed_dim, device=device, seed=_subseed(self._gen))
         F = self.embed_layer.n_fields
-        P = F * (F - 1) // 2
         self.inner_product_layer = InnerProductLayer(device=device)
         self.outer_product_layer = OuterProductLayer(device=device, seed=_subseed(self._gen))
+        dnn_seed = _subseed(self._gen)
+        if self.use_fgcnn:
+            self.fgcnn_layer = FGCNNLayer(**(fgcnn or {}), device=device, seed=_subseed(self._gen))
+            self.fgcnn_layer.build(F, embed_dim)
+            F += self.fgcnn_layer.n_new  # the product layers and the flat part see z
+        self.n_z = F
+        P = F * (F - 1) // 2
         if mode != "inner":
             self.outer_product_layer.build(F, embed_dim)
         self.width = F * embed_dim + P * (2 if mode == "both" else 1)
-        self.dnn_layer = DNNLayer(hidden_units, output_dim, activation, dropout, device=device,
-                                  seed=_subseed(self._gen))
+        self.dnn_layer = DNNLayer(hidden_units, output_dim, activation, dropout, device=device, seed=dnn_seed)
         self.dnn_layer.build(self.width)
         self._err = _ErrFlag(self._dev)
 
@@ -686,6 +701,20 @@ class PNN(KerasModule):
         e = self.embed_layer
         B = ids.shape[0]
         out = torch.empty(B, self.width, dtype=torch.float32, device=self._dev)
+        if self.use_fgcnn:
+            # z = [embed | fgcnn_out] [B, F', k]: the conv launch gathers embed into
+            # z and fills the pooled maps, each layer's Dense writes its new fields
+            # into z, then [flat | inner | outer] of z in one launch
+            fg = self.fgcnn_layer
+            z = torch.empty(B, self.n_z * e.k, dtype=torch.float32, device=self._dev)
+            ws = fg.conv_ids(ids, e, z, self._err.t)
+            fg.recombine(ws, z, col=e.n_fields * e.k)
+            call("rs_product_fwd", ptr(z), self.n_z, e.k, 1 if self.mode != "outer" else 0,
+                 ptr(self.outer_product_layer.prepared()) if self.mode != "inner" else None, ptr(out),
+                 out.stride(0), B, _lib.stream())
+            if check_ids:
+                self._err.check("PNN")
+            return out
         hoff, hvoc = e.host_meta()  # field metadata also by value (the kernel-argument front end)
         if self.mode == "inner":
             call("rs_embed_inner_fwd_hm", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(e.table),
@@ -722,6 +751,8 @@ class PNN(KerasModule):
           Dropout is the identity there too.  Returns the per-sample losses
           (before the step) if ``return_loss``."""
         dnn = self.dnn_layer
+        if self.use_fgcnn:
+            raise NotImplementedError("PNN.train_step: use_fgcnn")
         if dnn.output_layer.units != 1:
             raise NotImplementedError("PNN.train_step: output_dim 1 only")
         _check_train_tower("PNN", dnn)
