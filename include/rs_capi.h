@@ -604,6 +604,70 @@ int rs_mlp_affine_pieces_fwd(const float* x, int64_t x_stride,
                              const float* const* tables, const int64_t* vocabs,
                              int* err_flag, rs_stream_t stream);
 
+/* ------------------------------------- residual tower (DeepCrossing, a16)
+ * ResLayer.call (layer/interaction.py:261-278) on x [B, d]:
+ *   h = x;  h = relu(h @ W_i + b_i) for each hidden width;  h = h @ W_out + b_out
+ *   (W_out [last, d], no activation);  result = relu(x + h)
+ * stacked n_units times, each unit with its own weights but the same widths
+ * (model/deepCrossing.py:15-32), in ONE launch; a 16-sample tile stays in LDS
+ * from the input to the result and the skip operand stays in registers.
+ * hidden: host int[n_hidden], n_hidden 1..4; n_units 1..16; d and every
+ * width 1..1024.  rs_res_tower_ok: 1 when the shape is supported (the real
+ * LDS geometry), else 0.
+ * prepared (rs_res_tower_prepared_size floats, -1 on a bad shape) =
+ *   n_units * sum_l (Kp_l * Np_l + Np_l) + head * (roundup(d, 16) + 16)
+ * over the n_hidden + 1 layers of a unit, Kp / Np = a layer's input / output
+ * width rounded up to 16.  rs_res_tower_prepare packs it: W / bias are host
+ * arrays of n_units * (n_hidden + 1) device pointers, unit-major (Keras
+ * kernels [in, out]; bias, or any bias[i], may be NULL = zeros); head_w [d],
+ * head_b [1] (NULL = 0) are the model's Dense(1) — head_w NULL packs no head.
+ * rs_res_tower_fwd: head 0: y [B, d] (rows y_stride apart) = the last unit's
+ * output; head 1: y[b * y_stride] = sigmoid(x_L[b] . head_w + head_b)
+ * (prepared must hold the head; an image packed with the head serves head 0
+ * too).
+ * rs_deepcrossing_fwd: DeepCrossing.call from the ids — x = [dense (nd) |
+ * EmbedLayer rows (n_fields * k)] is staged straight into the input tile (the
+ * concat is never written; gather arguments as rs_embed_gather, an
+ * out-of-range id reads a zero row and sets *err_flag), then the units and
+ * the head: out [B]; x_last (optional, [B, d], rows x_last_stride apart)
+ * receives the last unit's output.  prepared must hold the head.
+ * Bit-identical to rs_res_tower_fwd on the same x.                          */
+int rs_res_tower_ok(int d, int n_hidden, const int* hidden, int n_units);
+int64_t rs_res_tower_prepared_size(int d, int n_hidden, const int* hidden,
+                                   int n_units, int head);
+int rs_res_tower_prepare(int d, int n_hidden, const int* hidden, int n_units,
+                         const float* const* W, const float* const* bias,
+                         const float* head_w, const float* head_b,
+                         float* prepared, rs_stream_t stream);
+int rs_res_tower_fwd(const float* x, int64_t x_stride, int d, int n_hidden,
+                     const int* hidden, int n_units, const float* prepared,
+                     int head, float* y, int64_t y_stride, int64_t batch,
+                     rs_stream_t stream);
+int rs_deepcrossing_fwd(const void* ids, int id_kind, int64_t id_stride,
+                        const float* dense, int64_t dense_stride, int nd,
+                        const float* table, const int64_t* field_offsets,
+                        const int64_t* field_vocab, int n_fields, int k,
+                        int n_hidden, const int* hidden, int n_units,
+                        const float* prepared, float* out, float* x_last,
+                        int64_t x_last_stride, int64_t batch, int* err_flag,
+                        rs_stream_t stream);
+
+/* ------------------------------------------ wide part of Wide&Deep (a17)
+ * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
+ * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense
+ * again (nd) | one-hot], one 1 per field at column 2 nd + field_offsets[c] +
+ * id(b, c):
+ *   logit[b] = w0 + sum_j dense[b,j] (w[j] + w[nd+j]) + sum_c w[2 nd + off_c + id_c]
+ * summed in that order.  field_widths[c] = the field's one-hot width; a code
+ * outside [0, width_c) contributes 0 and sets *err_flag.  w [2 nd + sum of
+ * the widths], w0 [1].  No one-hot matrix is formed.                        */
+int rs_wide_onehot_fwd(const void* ids, int id_kind, int64_t id_stride,
+                       const float* dense, int64_t dense_stride, int nd,
+                       const int64_t* field_offsets,
+                       const int64_t* field_widths, int n_fields,
+                       const float* w, const float* w0, float* logit,
+                       int64_t batch, int* err_flag, rs_stream_t stream);
+
 /* --------------------------------------------- fused DeepFM forward (a8)
  * DeepFM.call (model/deepFM.py:23-31) in ONE launch: ids -> rows -> x (kept
  * in LDS) -> FM logit and the DNN tower -> out[b] = sigmoid(c0*dnn + c1*fm)

@@ -87,6 +87,12 @@ SIGNATURES = {
     "rs_mlp_fwd": (I, [P, L, I, P, P, P, P, L, I, P, F, F, L, P]),
     "rs_mlp_affine_fwd": (I, [P, L, P, P, I, P, P, P, P, L, I, P, F, F, L, P]),
     "rs_mlp_affine_pieces_fwd": (I, [P, L, P, P, I, P, P, P, P, L, I, P, F, F, L, I, P, P, P, P, P, P, P, P, P]),
+    "rs_res_tower_ok": (I, [I, I, P, I]),
+    "rs_res_tower_prepared_size": (L, [I, I, P, I, I]),
+    "rs_res_tower_prepare": (I, [I, I, P, I, P, P, P, P, P, P]),
+    "rs_res_tower_fwd": (I, [P, L, I, I, P, I, P, I, P, L, L, P]),
+    "rs_deepcrossing_fwd": (I, [P, I, L, P, L, I, P, P, P, I, I, I, P, I, P, P, P, L, L, P, P]),
+    "rs_wide_onehot_fwd": (I, [P, I, L, P, L, I, P, P, I, P, P, P, L, P, P]),
     "rs_concat_pieces": (I, [I, P, P, P, P, P, P, P, P, L, L, P, P]),
     "rs_deepfm_fused_ok": (I, [I, I, I, I, I, P]),
     "rs_deepfm_fwd": (I, [P, I, L, P, L, I, P, P, P, I, I, P, P, I, I, P, P, P, F, F, P, P, L, P, P]),

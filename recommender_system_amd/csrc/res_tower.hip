@@ -1,0 +1,452 @@
+// res_tower.hip — DeepCrossing's stack of residual units in one launch:
+// ResLayer (layer/interaction.py:261-278: Dense(h_i, relu) per hidden width,
+// a linear Dense(d), then relu(x + h)) stacked n_units times
+// (model/deepCrossing.py:15-32), optionally closed by the model's
+// Dense(1, sigmoid) head.
+//
+// Layout and schedule (gfx950), on the fused MLP tower's machinery
+// (mlp_tower.hpp: B-fragment packing, weight ring, tile x k-slice work split
+// with its fixed-order reduction):
+//   * A workgroup owns 16 samples and 16 waves.  The 16 x d input tile is
+//     staged in LDS once — from x, or straight from the ids as [dense | rows]
+//     (rs_deepcrossing_fwd: the concat is never written) — and every layer of
+//     every unit reads its input tile from LDS and writes its result back to
+//     LDS (two ping-pong buffers): no activation touches HBM.
+//   * The skip operand.  A unit's input must outlive its n_hidden + 1 layers
+//     while both buffers are overwritten.  It is held in REGISTERS, by the
+//     thread that will finish that element: the last layer of a unit is d wide,
+//     so wave w finishes output tiles w, w + 16, ... (<= 4 of them at d <=
+//     1024: 16 floats per thread), or, when the layer is narrower than 4
+//     tiles and its k-slices meet in LDS, thread e finishes element e of the
+//     reduction (1 float).  Each thread reads exactly those elements of the
+//     unit's input tile after the barrier that opens the unit's first layer.
+//     A third LDS tile would not fit beside two 1024-wide ones (3 x 66 KB);
+//     the registers cost nothing at the widths that matter and leave the LDS
+//     budget, and so the occupancy, of the plain tower.
+//   * The skip-add epilogue relu(x_u + (acc + bias)) runs where the last
+//     layer's tile is finished; the padded columns (d..roundup(d,16)) come out
+//     as relu(0 + (0 + 0)) = 0 — packed weights, bias and skip are all zero
+//     there — so every column a later layer reads has been written.
+//   * Biases are read from the packed image (L2) by the finishing lane, the
+//     load in flight over the contraction: 16 units' biases need no LDS.
+//   * Every sum has one fixed order; a row's result does not depend on the
+//     batch or on the row's place in its tile.
+#include "mlp_tower.hpp"
+
+namespace rs {
+
+constexpr int RES_MAXH = 4;             // hidden layers per unit
+constexpr int RES_MAXL = RES_MAXH + 1;  // ... plus the linear Dense(d)
+constexpr int RES_MAXU = 16;            // units per launch
+constexpr int RES_NW = MLP_NW;
+constexpr int RES_SKIP = MLP_MAXD / 16 / RES_NW;  // output tiles of a d-wide layer per wave
+
+// prepared = [unit_0 .. unit_{U-1} | head_w (dp) | head_b (16)], the head part
+// only when head == 1; unit = [W_0 .. W_{nl-1} (packed) | bias_0 .. bias_{nl-1}
+// (Np_l each)].  Every block is a multiple of 16 floats.
+struct ResGeom {
+  int nl, n_units, d, dp;
+  int K[RES_MAXL], N[RES_MAXL], Kp[RES_MAXL], Np[RES_MAXL];
+  int64_t off[RES_MAXL];   // floats from the unit's base: packed W of layer l
+  int64_t boff[RES_MAXL];  // ... bias of layer l
+  int64_t unit, head_off, total;
+  int rs;      // LDS row stride (floats) of the activation buffers
+  size_t lds;  // dynamic LDS bytes
+};
+
+static bool res_geom(int d, int n_hidden, const int* hidden, int n_units, int head, ResGeom& g) {
+  if (n_hidden < 1 || n_hidden > RES_MAXH || n_units < 1 || n_units > RES_MAXU || !hidden) return false;
+  if (d < 1 || d > MLP_MAXD || (head != 0 && head != 1)) return false;
+  g.nl = n_hidden + 1;
+  g.n_units = n_units;
+  g.d = d;
+  g.dp = rup(d, 16);
+  int maxw = g.dp;
+  int64_t off = 0;
+  for (int l = 0; l < g.nl; ++l) {
+    const int kin = l == 0 ? d : hidden[l - 1], nout = l == n_hidden ? d : hidden[l];
+    if (nout < 1 || nout > MLP_MAXD) return false;
+    g.K[l] = kin;
+    g.N[l] = nout;
+    g.Kp[l] = rup(kin, 16);
+    g.Np[l] = rup(nout, 16);
+    g.off[l] = off;
+    off += (int64_t)g.Kp[l] * g.Np[l];
+    maxw = std::max(maxw, g.Np[l]);
+  }
+  for (int l = 0; l < g.nl; ++l) {
+    g.boff[l] = off;
+    off += g.Np[l];
+  }
+  g.unit = off;
+  g.head_off = off * n_units;
+  g.total = g.head_off + (head ? g.dp + 16 : 0);
+  g.rs = rup(maxw, 64) + 8;  // 8 (mod 64) dwords: conflict-free ds_read_b128 (mlp_geom)
+  g.lds = (size_t)(32 * g.rs + RES_NW * 256) * sizeof(float);
+  return g.lds <= 160 * 1024;
+}
+
+struct ResPrepArgs {
+  const float* W[RES_MAXL];
+  const float* bias[RES_MAXL];
+  ResGeom g;
+  float* out;  // the unit's base
+};
+
+__global__ void res_prepare_unit(ResPrepArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.g.unit) return;
+  float v = 0.f;
+  if (i < a.g.boff[0]) {
+    int l = 0;
+    while (l + 1 < a.g.nl && i >= a.g.off[l + 1]) ++l;
+    const int64_t r = i - a.g.off[l];
+    const int K = a.g.K[l], N = a.g.N[l], G = a.g.Kp[l] / 16;
+    // lane `lane` of k-group gg, output tile t holds W[16 gg + 4 (lane >> 4) + j][16 t + (lane & 15)]
+    const int j = (int)(r & 3), lane = (int)((r >> 2) & 63);
+    const int64_t blk = r >> 8;
+    const int gg = (int)(blk % G), t = (int)(blk / G);
+    const int k = 16 * gg + 4 * (lane >> 4) + j, n = 16 * t + (lane & 15);
+    if (k < K && n < N) v = a.W[l][(int64_t)k * N + n];
+  } else {
+    int l = 0;
+    while (l + 1 < a.g.nl && i >= a.g.boff[l + 1]) ++l;
+    const int n = (int)(i - a.g.boff[l]);
+    v = (n < a.g.N[l] && a.bias[l]) ? a.bias[l][n] : 0.f;
+  }
+  a.out[i] = v;
+}
+
+__global__ void res_prepare_head(const float* w, const float* b, int d, int dp, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= dp + 16) return;
+  out[i] = i < d ? w[i] : (i == dp && b ? b[0] : 0.f);
+}
+
+struct ResArgs {
+  // the input tile: x [M, d] (KIND 3), or [dense | rows] from the ids
+  const float* x;
+  int64_t xs;
+  const void* ids;
+  int64_t id_stride;
+  const float* dense;
+  int64_t dense_stride;
+  int nd;
+  const float* table;
+  const int64_t* offs;
+  const int64_t* vocab;
+  int F, k;
+  int* err;
+  const float* prep;
+  int d, dp, nl, n_units, rs, unroll;
+  int Kp[RES_MAXL], Np[RES_MAXL];
+  int64_t off[RES_MAXL], boff[RES_MAXL], unit, head_off;
+  float* xl;  // the last unit's output [M, d], rows xls apart (null: not written)
+  int64_t xls;
+  float* yh;  // sigmoid(x_L . head_w + head_b) [M], yhs apart (null: no head)
+  int64_t yhs;
+  int64_t M;
+};
+
+// this wave's first item of layer l of unit u: its ring, requested early
+template <int NW>
+__device__ __forceinline__ void res_first_fill(const ResArgs& a, int u, int l, floatx4 (&ring)[MLP_R]) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int T = a.Np[l] >> 4, G = a.Kp[l] >> 4;
+  const int S = mlp_slices(T, G, NW);
+  if (w < T * S) {
+    const MlpItem it = mlp_item(w, T, G, S);
+    mlp_ring_fill(ring,
+                  reinterpret_cast<const floatx4*>(a.prep + u * a.unit + a.off[l]) + lane + (int64_t)it.t * G * 64,
+                  it.g0, it.g1);
+  }
+}
+
+__device__ __forceinline__ floatx4 res_pick(const floatx4 (&s)[RES_SKIP], int i) {
+  static_assert(RES_SKIP == 4, "four skip tiles per wave");
+  return i == 0 ? s[0] : (i == 1 ? s[1] : (i == 2 ? s[2] : s[3]));
+}
+
+template <int NW, int KIND>
+__global__ __launch_bounds__(NW * 64) void res_tower(ResArgs a) {
+  extern __shared__ float smem[];
+  const int RS = a.rs;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t m0 = (int64_t)blockIdx.x * 16;
+
+  // the first layer's weights first (independent of everything), then the
+  // input tile, one row per wave; rows past M re-read row M-1 and are never
+  // stored; columns d .. dp-1 are zeros
+  floatx4 ring[MLP_R];
+  res_first_fill<NW>(a, 0, 0, ring);
+  for (int r = w; r < 16; r += NW) {
+    const int64_t m = m0 + r < a.M ? m0 + r : a.M - 1;
+    if constexpr (KIND == 3) {
+      const float* xr = a.x + m * a.xs;
+      for (int c = lane; c < a.dp; c += 64) smem[r * RS + c] = c < a.d ? xr[c] : 0.f;
+    } else {
+      typedef Ids<KIND> I;
+      bool bad = false;
+      for (int c = lane; c < a.dp; c += 64) {
+        float v = 0.f;
+        if (c < a.nd) {
+          v = a.dense[m * a.dense_stride + c];
+        } else if (c < a.d) {
+          const int f = (c - a.nd) / a.k, j = (c - a.nd) - f * a.k;
+          int64_t id;
+          const bool ok = I::decode(I::load(a.ids, m * a.id_stride + f), a.vocab[f], id);
+          v = ok ? a.table[(a.offs[f] + id) * a.k + j] : 0.f;
+          bad |= !ok;
+        }
+        smem[r * RS + c] = v;
+      }
+      if (__any(bad) && lane == 0) flag_error(a.err);
+    }
+  }
+
+  float* in = smem;
+  float* out = smem + 16 * RS;
+  float* red = smem + 32 * RS;
+  const int LL = a.nl - 1;
+  // the work split of a unit's last (d-wide) layer decides who holds the skip
+  const int TL = a.Np[LL] >> 4;
+  const int SL = mlp_slices(TL, a.Kp[LL] >> 4, NW);
+  for (int u = 0; u < a.n_units; ++u) {
+    const float* up = a.prep + u * a.unit;
+    const bool final_unit = u == a.n_units - 1;
+    floatx4 skip[RES_SKIP];
+#pragma unroll
+    for (int i = 0; i < RES_SKIP; ++i) skip[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int l = 0; l < a.nl; ++l) {
+      const int T = a.Np[l] >> 4, G = a.Kp[l] >> 4;
+      const int S = mlp_slices(T, G, NW);
+      __syncthreads();  // the layer's input complete
+      if (l == 0) {
+        // the unit's input, by the thread that will add it back (`in` is not
+        // written before the next layer's barrier)
+        if (SL == 1) {
+#pragma unroll
+          for (int i = 0; i < RES_SKIP; ++i) {
+            const int t = w + NW * i;
+            if (t < TL) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) skip[i][r] = in[(4 * (lane >> 4) + r) * RS + 16 * t + (lane & 15)];
+            }
+          }
+        } else if ((int)threadIdx.x < TL * 256) {
+          const int e = threadIdx.x, t = e >> 8, ln = (e & 255) >> 2, r = e & 3;
+          skip[0][0] = in[(4 * (ln >> 4) + r) * RS + 16 * t + (ln & 15)];
+        }
+      }
+      const floatx4* W = reinterpret_cast<const floatx4*>(up + a.off[l]) + lane;
+      const float* bias = up + a.boff[l];
+      const bool last = l == LL;
+      // one finished element: hidden layers relu(v + b); the unit's last layer
+      // relu(x_u + (v + b)), also to x_L when this is the last unit
+      auto finish = [&](int row, int col, float v, float bc, float sk) {
+        if (!last) {
+          out[row * RS + col] = fmaxf(v + bc, 0.f);
+        } else {
+          const float y = fmaxf(sk + (v + bc), 0.f);
+          out[row * RS + col] = y;
+          const int64_t m = m0 + row;
+          if (final_unit && a.xl && m < a.M && col < a.d) a.xl[m * a.xls + col] = y;
+        }
+      };
+
+      const float* ap = in + (lane & 15) * RS + 4 * (lane >> 4);
+      int i = 0;
+      for (int item = w; item < T * S; item += NW, ++i) {
+        const MlpItem it = mlp_item(item, T, G, S);
+        const floatx4* bp = W + (int64_t)it.t * G * 64;
+        if (item != w) mlp_ring_fill(ring, bp, it.g0, it.g1);
+        const int col = 16 * it.t + (lane & 15);
+        const float bc = bias[col];  // in flight over the contraction
+        floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+        mlp_mac(ring, ap, bp, it.g0, it.g1, acc, a.unroll);
+        if (S == 1) {
+          const floatx4 sk = res_pick(skip, i);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) finish(4 * (lane >> 4) + r, col, acc[r], bc, sk[r]);
+        } else {
+          *reinterpret_cast<floatx4*>(red + item * 256 + lane * 4) = acc;
+        }
+      }
+      // the next layer's first weights (the next unit's, after the last
+      // layer) do not depend on this layer: request them now
+      if (l + 1 < a.nl) res_first_fill<NW>(a, u, l + 1, ring);
+      else if (!final_unit) res_first_fill<NW>(a, u + 1, 0, ring);
+      if (S > 1) {
+        __syncthreads();  // the partial tiles in red
+        for (int e = threadIdx.x; e < T * 256; e += NW * 64) {
+          const int t = e >> 8, q = e & 255, ln = q >> 2, r = q & 3;
+          float v = 0.f;
+          for (int p = 0; p < S; ++p) v += red[(p * T + t) * 256 + q];
+          const int col = 16 * t + (ln & 15);
+          finish(4 * (ln >> 4) + r, col, v, bias[col], skip[0][0]);
+        }
+      }
+      float* tmp = in;
+      in = out;
+      out = tmp;
+    }
+  }
+  if (a.yh) {
+    // the head: one sample row per wave, columns in lane order then a fixed
+    // butterfly (the padded columns of x_L and of head_w are zeros)
+    __syncthreads();
+    const float* hw = a.prep + a.head_off;
+    for (int r = w; r < 16; r += NW) {
+      float z = 0.f;
+      for (int c = lane; c < a.dp; c += 64) z = fmaf(in[r * RS + c], hw[c], z);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+      const int64_t m = m0 + r;
+      if (lane == 0 && m < a.M) a.yh[m * a.yhs] = sigmoidf_(z + hw[a.dp]);
+    }
+  }
+}
+
+static void res_fill_args(const ResGeom& g, const float* prepared, ResArgs& a) {
+  for (int l = 0; l < g.nl; ++l) {
+    a.Kp[l] = g.Kp[l];
+    a.Np[l] = g.Np[l];
+    a.off[l] = g.off[l];
+    a.boff[l] = g.boff[l];
+  }
+  a.prep = prepared;
+  a.d = g.d;
+  a.dp = g.dp;
+  a.nl = g.nl;
+  a.n_units = g.n_units;
+  a.rs = g.rs;
+  a.unit = g.unit;
+  a.head_off = g.head_off;
+  a.unroll = opt(RS_OPT_MLP_UNROLL);
+}
+
+template <int KIND>
+static int res_launch(const ResArgs& a, const ResGeom& g, rs_stream_t stream, const char* what) {
+  const int64_t grid = (a.M + 15) / 16;
+  RS_REQUIRE(grid < (1ll << 31), "%s: batch too large", what);
+  static LdsAttr lds_set;
+  lds_attr(lds_set, (const void*)res_tower<RES_NW, KIND>, g.lds);
+  res_tower<RES_NW, KIND><<<(unsigned)grid, RES_NW * 64, g.lds, as_stream(stream)>>>(a);
+  return launch_status(what);
+}
+
+}  // namespace rs
+
+using namespace rs;
+
+#define RES_SHAPE_MSG "need 1..%d hidden widths, 1..%d units, widths 1..%d"
+
+extern "C" int rs_res_tower_ok(int d, int n_hidden, const int* hidden, int n_units) {
+  ResGeom g;
+  return res_geom(d, n_hidden, hidden, n_units, 0, g) ? 1 : 0;
+}
+
+extern "C" int64_t rs_res_tower_prepared_size(int d, int n_hidden, const int* hidden, int n_units, int head) {
+  ResGeom g;
+  if (!res_geom(d, n_hidden, hidden, n_units, head, g)) {
+    set_error("rs_res_tower_prepared_size: " RES_SHAPE_MSG " (head 0 or 1)", RES_MAXH, RES_MAXU, MLP_MAXD);
+    return -1;
+  }
+  return g.total;
+}
+
+extern "C" int rs_res_tower_prepare(int d, int n_hidden, const int* hidden, int n_units, const float* const* W,
+                                    const float* const* bias, const float* head_w, const float* head_b,
+                                    float* prepared, rs_stream_t stream) {
+  ResGeom g;
+  const int head = head_w ? 1 : 0;
+  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, head, g), "rs_res_tower_prepare: " RES_SHAPE_MSG, RES_MAXH,
+             RES_MAXU, MLP_MAXD);
+  RS_REQUIRE(W && prepared, "rs_res_tower_prepare: null pointer");
+  RS_REQUIRE(head_w || !head_b, "rs_res_tower_prepare: head_b without head_w");
+  for (int i = 0; i < n_units * g.nl; ++i)
+    RS_REQUIRE(W[i], "rs_res_tower_prepare: unit %d layer %d has no kernel", i / g.nl, i % g.nl);
+  for (int u = 0; u < n_units; ++u) {
+    ResPrepArgs a{};
+    for (int l = 0; l < g.nl; ++l) {
+      a.W[l] = W[u * g.nl + l];
+      a.bias[l] = bias ? bias[u * g.nl + l] : nullptr;
+    }
+    a.g = g;
+    a.out = prepared + u * g.unit;
+    res_prepare_unit<<<(unsigned)((g.unit + 255) / 256), 256, 0, as_stream(stream)>>>(a);
+  }
+  if (head)
+    res_prepare_head<<<(g.dp + 16 + 255) / 256, 256, 0, as_stream(stream)>>>(head_w, head_b, g.d, g.dp,
+                                                                           prepared + g.head_off);
+  return launch_status("rs_res_tower_prepare");
+}
+
+extern "C" int rs_res_tower_fwd(const float* x, int64_t x_stride, int d, int n_hidden, const int* hidden,
+                                int n_units, const float* prepared, int head, float* y, int64_t y_stride,
+                                int64_t batch, rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  ResGeom g;
+  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, head, g), "rs_res_tower_fwd: " RES_SHAPE_MSG " (head 0 or 1)",
+             RES_MAXH, RES_MAXU, MLP_MAXD);
+  RS_REQUIRE(x && prepared && y, "rs_res_tower_fwd: null pointer");
+  RS_REQUIRE(batch >= 0 && x_stride >= d, "rs_res_tower_fwd: bad batch/stride (x_stride < d)");
+  RS_REQUIRE(y_stride >= (head ? 1 : d), "rs_res_tower_fwd: y_stride too small");
+  ResArgs a{};
+  res_fill_args(g, prepared, a);
+  a.x = x;
+  a.xs = x_stride;
+  if (head) {
+    a.yh = y;
+    a.yhs = y_stride;
+  } else {
+    a.xl = y;
+    a.xls = y_stride;
+  }
+  a.M = batch;
+  return res_launch<3>(a, g, stream, "rs_res_tower_fwd");
+}
+
+extern "C" int rs_deepcrossing_fwd(const void* ids, int id_kind, int64_t id_stride, const float* dense,
+                                   int64_t dense_stride, int nd, const float* table, const int64_t* field_offsets,
+                                   const int64_t* field_vocab, int n_fields, int k, int n_hidden, const int* hidden,
+                                   int n_units, const float* prepared, float* out, float* x_last,
+                                   int64_t x_last_stride, int64_t batch, int* err_flag, rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  RS_REQUIRE(batch >= 0 && nd >= 0 && n_fields >= 1 && k >= 1 && n_fields <= MLP_MAXD && k <= MLP_MAXD,
+             "rs_deepcrossing_fwd: bad shape");
+  const int d = nd + n_fields * k;
+  ResGeom g;
+  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, 1, g),
+             "rs_deepcrossing_fwd: " RES_SHAPE_MSG " (input width nd + n_fields * k)", RES_MAXH, RES_MAXU, MLP_MAXD);
+  RS_REQUIRE(ids && table && field_offsets && field_vocab && prepared && out && (nd == 0 || dense),
+             "rs_deepcrossing_fwd: null pointer");
+  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_deepcrossing_fwd: bad id_kind");
+  RS_REQUIRE(id_stride >= n_fields && (nd == 0 || dense_stride >= nd),
+             "rs_deepcrossing_fwd: id_stride / dense_stride smaller than the width");
+  RS_REQUIRE(!x_last || x_last_stride >= d, "rs_deepcrossing_fwd: x_last_stride too small");
+  RS_REQUIRE((uintptr_t)table % 16 == 0, "rs_deepcrossing_fwd: table must be 16-B aligned");
+  ResArgs a{};
+  res_fill_args(g, prepared, a);
+  a.ids = ids;
+  a.id_stride = id_stride;
+  a.dense = dense;
+  a.dense_stride = dense_stride;
+  a.nd = nd;
+  a.table = table;
+  a.offs = field_offsets;
+  a.vocab = field_vocab;
+  a.F = n_fields;
+  a.k = k;
+  a.err = err_flag;
+  a.xl = x_last;
+  a.xls = x_last_stride;
+  a.yh = out;
+  a.yhs = 1;
+  a.M = batch;
+  int st = RS_OK;
+  with_id_kind(id_kind, [&](auto K) { st = res_launch<decltype(K)::value>(a, g, stream, "rs_deepcrossing_fwd"); });
+  return st;
+}

@@ -13,6 +13,8 @@ Each class keeps the reference layer's name, constructor arguments and
                                               layer/interaction.py:30-46
   Attention(hidden_units, activation='prelu') layer/interaction.py:355-406
   Dice(axis=-1, epsilon=1e-9)                 layer/interaction.py:410-425
+  ResLayer(hidden_units)                      layer/interaction.py:261-278
+  WideLayer()                                 layer/interaction.py:11-26
   Dense / PReLU / BatchNormalization          the Keras layers the models use
 
 Weights are built lazily on the first call from the input shape, like Keras
@@ -1167,3 +1169,202 @@ class FFMLayer(KerasModule):
 
     def forward(self, inputs):
         return self.logits(inputs, 0)
+
+
+# ------------------------------------------------- DeepCrossing / Wide&Deep
+_RES_MAXH, _RES_MAXU = 4, 16  # res_tower.hip RES_MAXH / RES_MAXU
+
+
+def _res_ok(d, hidden, n_units):
+    return bool(_lib.lib().rs_res_tower_ok(int(d), len(hidden), (C.c_int * max(len(hidden), 1))(*hidden),
+                                           int(n_units)))
+
+
+def _res_prepare(units, head, device):
+    """The packed image (rs_res_tower_prepare) of a stack of built ResLayers
+    with equal widths, optionally with the model's Dense(1) head."""
+    d, hidden = units[0].input_dim, units[0].hidden_units
+    nh, nu = len(hidden), len(units)
+    ci = (C.c_int * nh)(*hidden)
+    size = _lib.lib().rs_res_tower_prepared_size(d, nh, ci, nu, 1 if head is not None else 0)
+    if size < 0:
+        _lib.check(-1, "rs_res_tower_prepared_size")
+    layers = [l for u in units for l in u._layers()]
+    pa = lambda ts: (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
+    prep = torch.empty(size, dtype=torch.float32, device=device)
+    call("rs_res_tower_prepare", d, nh, ci, nu, pa([l.kernel for l in layers]), pa([l.bias for l in layers]),
+         ptr(head.kernel) if head is not None else None, ptr(head.bias) if head is not None else None, ptr(prep),
+         _stream())
+    return prep
+
+
+def _res_key(layers):
+    return tuple((p._version, p.data_ptr()) for l in layers for p in (l.kernel, l.bias))
+
+
+class ResLayer(KerasModule):
+    """ResLayer(hidden_units) — layer/interaction.py:261-278: h = x through
+    Dense(u, relu) per hidden width, then a linear Dense(d) (built from the
+    input width on the first call or by ``build(d)``); relu(x + h).
+
+    ``forward(x[B, d])`` is ONE rs_res_tower_fwd launch (res_tower.hip: the
+    tile stays in LDS, the skip operand in registers) when the shape is
+    supported and x is a device tensor with contiguous rows; otherwise
+    rs_dense_fwd per layer plus a torch add / relu."""
+
+    def __init__(self, hidden_units, device=None, seed=None):
+        super().__init__(device, seed)
+        self.hidden_units = [int(u) for u in hidden_units]
+        self.dense_layer = nn.ModuleList(
+            [Dense(u, activation="relu", device=device, seed=_subseed(self._gen)) for u in self.hidden_units])
+        self._out_seed = _subseed(self._gen)
+        self.output_layer = None
+        self.input_dim = None
+
+    @property
+    def built(self):
+        return self.output_layer is not None
+
+    def build(self, d):
+        d = int(d)
+        n = d
+        for layer in self.dense_layer:
+            layer.build(n)
+            n = layer.units
+        self.output_layer = Dense(d, activation=None, device=self._dev, seed=self._out_seed, input_dim=n)
+        self.input_dim = d
+        self._invalidate()
+
+    def _layers(self):
+        return list(self.dense_layer) + [self.output_layer]
+
+    def _invalidate(self):
+        self.__dict__.pop("_res_prep", None)
+
+    def keras_weights(self):
+        if not self.built:
+            raise RuntimeError("ResLayer: not built (call build(d) or run a forward first)")
+        out = {}
+        for i, l in enumerate(self.dense_layer):
+            out[f"dense_{i}/kernel"], out[f"dense_{i}/bias"] = l.kernel, l.bias
+        out["dense_out/kernel"], out["dense_out/bias"] = self.output_layer.kernel, self.output_layer.bias
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        own = self.keras_weights()
+        if strict and set(own) != set(weights):
+            raise KeyError(f"ResLayer: expected weights {sorted(own)}, got {sorted(weights)}")
+        with torch.no_grad():
+            for name, p in own.items():
+                if name in weights:
+                    p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
+        self._invalidate()
+
+    def tower_ok(self):
+        return self.built and len(self.hidden_units) >= 1 and _res_ok(self.input_dim, self.hidden_units, 1)
+
+    def prepared(self):
+        """Weights packed for rs_res_tower_fwd, cached until a weight changes."""
+        key = _res_key(self._layers())
+        ent = self.__dict__.get("_res_prep")
+        if ent is None or ent[0] != key:
+            ent = self.__dict__["_res_prep"] = (key, _res_prepare([self], None, self._dev))
+        return ent[1]
+
+    def forward_layers(self, x):
+        """The per-layer composition: rs_dense_fwd per Dense, torch add / relu."""
+        h = x
+        for layer in self._layers():
+            h = layer(h)
+        return torch.relu(x + h)
+
+    def forward(self, inputs):
+        x = inputs if (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32) \
+            else _to_device_f32(inputs, self._dev)
+        if not self.built:
+            self.build(x.shape[-1])
+        B, d = x.shape
+        if d != self.input_dim:
+            raise ValueError(f"ResLayer built for {self.input_dim} inputs, got {d}")
+        if not (x.is_cuda and x.stride(1) == 1 and self.tower_ok()):
+            return self.forward_layers(x)
+        out = torch.empty(B, d, dtype=torch.float32, device=self._dev)
+        nh = len(self.hidden_units)
+        call("rs_res_tower_fwd", ptr(x), x.stride(0), d, nh, (C.c_int * nh)(*self.hidden_units), 1,
+             ptr(self.prepared()), 0, ptr(out), out.stride(0), B, _stream())
+        return out
+
+
+class WideLayer(KerasModule):
+    """WideLayer() — layer/interaction.py:11-26: w0 + x @ w with w0 (1,)
+    zeros and w (n, 1) ~ N(0, 0.05), built from the input width on the first
+    call.  ``forward(x[B, n])`` is rs_dense_fwd with one output unit (w0 as
+    its bias).  ``forward_onehot(dense, ids, field_offsets, field_widths)``
+    takes the compact form of Wide&Deep's wide input [dense | dense | one-hot]
+    (model/wideDeep.py:22-27) and gathers one scalar of w per field
+    (rs_wide_onehot_fwd) instead of multiplying by zeros."""
+
+    def __init__(self, device=None, seed=None):
+        super().__init__(device, seed)
+        self.w0 = self.w = None
+
+    @property
+    def built(self):
+        return self.w is not None
+
+    def build(self, n):
+        self.w0 = nn.Parameter(torch.zeros(1, device=self._dev), requires_grad=False)
+        self.w = nn.Parameter(_normal((int(n), 1), self._gen, self._dev), requires_grad=False)
+
+    def keras_weights(self):
+        if not self.built:
+            raise RuntimeError("WideLayer: not built (call build(n) or run a forward first)")
+        return {"w0": self.w0, "w": self.w}
+
+    def set_keras_weights(self, weights, strict=True):
+        own = self.keras_weights()
+        if strict and set(own) != set(weights):
+            raise KeyError(f"WideLayer: expected weights {sorted(own)}, got {sorted(weights)}")
+        with torch.no_grad():
+            for name, p in own.items():
+                if name in weights:
+                    p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
+
+    def forward(self, inputs):
+        x = inputs if (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32) \
+            else _to_device_f32(inputs, self._dev)
+        if not self.built:
+            self.build(x.shape[-1])
+        B, n = x.shape
+        if n != self.w.shape[0]:
+            raise ValueError(f"WideLayer built for {self.w.shape[0]} inputs, got {n}")
+        out = torch.empty(B, 1, dtype=torch.float32, device=self._dev)
+        call("rs_dense_fwd", ptr(x), x.stride(0), ptr(self.w), ptr(self.w0), None, 0, ptr(out), 1, B, n, 1,
+             _stream())
+        return out
+
+    def forward_onehot(self, dense, ids, field_offsets, field_widths, check_ids=True):
+        ids = _ids_tensor(ids, self._dev)
+        B, F = ids.shape
+        offs = torch.as_tensor(field_offsets, dtype=torch.int64).to(self._dev)
+        wid = torch.as_tensor(field_widths, dtype=torch.int64).to(self._dev)
+        if dense is None:
+            nd = 0
+        else:
+            dense = _to_device_f32(dense, self._dev)
+            nd = dense.shape[1]
+        if offs.numel() != F or wid.numel() != F:
+            raise ValueError(f"WideLayer: {F} id columns need {F} field offsets and widths")
+        n = 2 * nd + int(wid.sum())  # (a host sum: not inside a graph capture)
+        if not self.built:
+            self.build(n)
+        if n != self.w.shape[0]:
+            raise ValueError(f"WideLayer built for {self.w.shape[0]} inputs, got 2*{nd} + {n - 2 * nd}")
+        out = torch.empty(B, 1, dtype=torch.float32, device=self._dev)
+        err = _ErrFlag(self._dev)
+        call("rs_wide_onehot_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense) if nd else None,
+             dense.stride(0) if nd else 0, nd, ptr(offs), ptr(wid), F, ptr(self.w), ptr(self.w0), ptr(out), B,
+             ptr(err.t), _stream())
+        if check_ids:
+            err.check("WideLayer")
+        return out

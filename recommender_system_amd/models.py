@@ -17,6 +17,8 @@ models (Hcyand/recommender_system, algorithm/deep_learning/model/):
                                                                   model/nfm.py:13-33
   AFM(feature_columns, mode)                                      model/afm.py:11-19
   FFM(feature_columns, k, w_reg=1e-4, v_reg=1e-4)                 model/ffm.py:10-22
+  DeepCrossing(feature_columns, k, hidden_units, res_layer_num)   model/deepCrossing.py:15-32
+  WideDeep(feature_columns, hidden_units, output_dim, activation) model/wideDeep.py:14-34
 
 Criteo-style models take the reference's packed input X[B, 13+F] (dense
 features followed by label-encoded sparse ids, as floats — Keras casts them to
@@ -45,7 +47,8 @@ from . import _lib
 from ._lib import call, ptr
 from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense, DNNLayer, EmbedLayer, FFMLayer,
                      FGCNNLayer, FMLayer, InnerProductLayer, OuterProductLayer,
-                     KerasModule, TowerMixin, sigmoid_combine, _ids_tensor, _to_device_f32, _ErrFlag)
+                     KerasModule, ResLayer, TowerMixin, WideLayer, sigmoid_combine, _ids_tensor, _to_device_f32,
+                     _ErrFlag, _RES_MAXH, _RES_MAXU, _res_key, _res_ok, _res_prepare)
 
 
 def _split_criteo(inputs, nd, device):
@@ -1439,3 +1442,207 @@ class FFM(KerasModule):
              ptr(L.field_offsets), ptr(L.field_vocab), F, B, ptr(g), 1, 0, float(lr), ptr(ws), None, st)
         self._weights_changed()
         return loss
+
+
+def _prefixed(prefix, weights):
+    return {f"{prefix}/{k}": v for k, v in weights.items()}
+
+
+def _set_prefixed(module, prefix, weights, strict):
+    """module.set_keras_weights on the entries of `weights` under prefix/."""
+    own = {k[len(prefix) + 1:]: v for k, v in weights.items() if k.startswith(prefix + "/")}
+    if not strict:
+        own = {k: v for k, v in own.items() if k in module.keras_weights()}
+    if strict:
+        missing = set(module.keras_weights()) - set(own)
+        if missing:
+            raise KeyError(f"missing weights {sorted(prefix + '/' + m for m in missing)}")
+    if own or strict:
+        module.set_keras_weights(own, strict)
+
+
+class DeepCrossing(KerasModule):
+    """DeepCrossing(feature_columns, k, hidden_units, res_layer_num) —
+    model/deepCrossing.py:15-32: x = [dense | EmbedLayer(sparse)] through
+    res_layer_num ResLayers (each with its own weights; one ``hidden_units``
+    serves them all, so units of differing shapes cannot occur), then
+    Dense(1, sigmoid).
+
+    ``k`` is accepted and ignored, as in the reference (its EmbedLayer keeps
+    the default width 8); the embedding width is ``embed_dim``.
+
+    ``forward_fused`` is ONE launch from the ids (rs_deepcrossing_fwd: the
+    concat is never written, every activation stays in LDS);
+    ``forward_unfused`` is the gather, one launch per unit (or the per-layer
+    composition where the tower kernel does not take the shape), then the
+    Dense + sigmoid.  ``forward`` takes the fused path when ``fused_ok()``."""
+
+    def __init__(self, feature_columns, k, hidden_units, res_layer_num, embed_dim=8, device=None, seed=None):
+        super().__init__(device, seed)
+        self.dense_feature_columns, self.sparse_feature_columns = feature_columns
+        self.nd = len(self.dense_feature_columns)
+        self.k = k  # unused, as in the reference
+        self.hidden_units = [int(u) for u in hidden_units]
+        self.embed_layer = EmbedLayer(self.sparse_feature_columns, embed_dim, device=device, seed=_subseed(self._gen))
+        self.d = self.nd + self.embed_layer.n_fields * self.embed_layer.k
+        self.res_layer = torch.nn.ModuleList(
+            [ResLayer(self.hidden_units, device=device, seed=_subseed(self._gen)) for _ in range(int(res_layer_num))])
+        for unit in self.res_layer:
+            unit.build(self.d)
+        self.output_layer = Dense(1, activation="sigmoid", device=device, seed=_subseed(self._gen), input_dim=self.d)
+        self._err = _ErrFlag(self._dev)
+
+    def keras_weights(self):
+        out = _prefixed("embed_layer", self.embed_layer.keras_weights())
+        for u, unit in enumerate(self.res_layer):
+            out.update(_prefixed(f"res_layer_{u}", unit.keras_weights()))
+        out.update(_prefixed("output_layer", self.output_layer.keras_weights()))
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        if strict:
+            unknown = set(weights) - set(self.keras_weights())
+            if unknown:
+                raise KeyError(f"unknown weights {sorted(unknown)}")
+        _set_prefixed(self.embed_layer, "embed_layer", weights, strict)
+        for u, unit in enumerate(self.res_layer):
+            _set_prefixed(unit, f"res_layer_{u}", weights, strict)
+        _set_prefixed(self.output_layer, "output_layer", weights, strict)
+        self._weights_changed()
+
+    def _invalidate(self):
+        self.__dict__.pop("_res_prep", None)
+
+    def _all_layers(self):
+        return [l for unit in self.res_layer for l in unit._layers()] + [self.output_layer]
+
+    def fused_ok(self):
+        n = len(self.res_layer)
+        return (1 <= n <= _RES_MAXU and 1 <= len(self.hidden_units) <= _RES_MAXH
+                and self.embed_layer.n_fields >= 1 and self.embed_layer.table.data_ptr() % 16 == 0
+                and _res_ok(self.d, self.hidden_units, n))
+
+    def prepared(self):
+        """Every unit's weights and the head packed for rs_deepcrossing_fwd,
+        cached until a weight changes."""
+        key = _res_key(self._all_layers())
+        ent = self.__dict__.get("_res_prep")
+        if ent is None or ent[0] != key:
+            ent = self.__dict__["_res_prep"] = (key, _res_prepare(list(self.res_layer), self.output_layer, self._dev))
+        return ent[1]
+
+    def forward_fused(self, inputs, check_ids=True, x_last=None):
+        """DeepCrossing.call as ONE kernel (rs_deepcrossing_fwd).  x_last
+        (optional, [B, d]) receives the last unit's output."""
+        dense, ids = _split_criteo(inputs, self.nd, self._dev)
+        B = ids.shape[0]
+        e = self.embed_layer
+        nh = len(self.hidden_units)
+        out = torch.empty(B, 1, dtype=torch.float32, device=self._dev)
+        call("rs_deepcrossing_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense) if self.nd else None,
+             dense.stride(0) if self.nd else 0, self.nd, ptr(e.table), ptr(e.field_offsets), ptr(e.field_vocab),
+             e.n_fields, e.k, nh, (C.c_int * nh)(*self.hidden_units), len(self.res_layer), ptr(self.prepared()),
+             ptr(out), ptr(x_last), 0 if x_last is None else x_last.stride(0), B, ptr(self._err.t), _lib.stream())
+        if check_ids:
+            self._err.check("DeepCrossing")
+        return out
+
+    def forward_unfused(self, inputs, check_ids=True):
+        """rs_embed_gather, one ResLayer forward per unit, Dense(1, sigmoid)."""
+        dense, ids = _split_criteo(inputs, self.nd, self._dev)
+        x = self.embed_layer.gather(ids, dense if self.nd else None, check_ids=check_ids)
+        for unit in self.res_layer:
+            x = unit(x)
+        return self.output_layer(x)
+
+    def forward(self, inputs, check_ids=True):
+        if self.fused_ok():
+            return self.forward_fused(inputs, check_ids)
+        return self.forward_unfused(inputs, check_ids)
+
+    def train_step(self, *args, **kwargs):
+        raise NotImplementedError("DeepCrossing.train_step: training DeepCrossing is not implemented (forward only)")
+
+
+def _packed_f32(x, device):
+    """The reference's packed matrix (dtype object / float64 from
+    create_criteo_dataset) as a device fp32 tensor (Keras' input autocast)."""
+    if not torch.is_tensor(x):
+        import numpy as np
+        x = np.asarray(x)
+        if x.dtype == object:
+            x = x.astype(np.float64)
+    return _to_device_f32(x, device)
+
+
+class WideDeep(KerasModule):
+    """WideDeep(feature_columns, hidden_units, output_dim, activation) —
+    model/wideDeep.py:14-34: sigmoid(0.5 * (WideLayer([dense | one-hot part])
+    + DNNLayer(EmbedLayer(sparse)))); the deep input is the embeddings only.
+
+    ``forward(X)`` takes the reference's packed row from
+    create_criteo_dataset('WideDeep'): [dense nd | label codes F | dense nd
+    again | dummies W] (get_dummies keeps the numeric columns, so the wide
+    input [X[:, :nd] | X[:, nd+F:]] holds the dense block twice).
+    ``forward_onehot(dense, ids, field_offsets, field_widths)`` takes the
+    compact form (dummies column of field c's code: field_offsets[c] + code)
+    and gathers the wide weights (rs_wide_onehot_fwd).  The wide weight w is
+    built on first use from the input width 2 nd + sum(widths).  With
+    output_dim == 1 the deep tower and the head are one rs_mlp_fwd launch;
+    otherwise the reference's broadcast [B,1] + [B,output_dim] applies."""
+
+    def __init__(self, feature_columns, hidden_units, output_dim, activation, embed_dim=8, device=None, seed=None):
+        super().__init__(device, seed)
+        self.dense_feature_columns, self.sparse_feature_columns = feature_columns
+        self.nd = len(self.dense_feature_columns)
+        self.embed_layer = EmbedLayer(self.sparse_feature_columns, embed_dim, device=device, seed=_subseed(self._gen))
+        self.wide = WideLayer(device=device, seed=_subseed(self._gen))
+        self.deep = DNNLayer(hidden_units, output_dim, activation, device=device, seed=_subseed(self._gen))
+        self.deep.build(self.embed_layer.n_fields * self.embed_layer.k)
+        self.output_dim = int(output_dim)
+
+    def build(self, wide_width):
+        """Build the wide weights for a wide input of `wide_width` columns."""
+        self.wide.build(wide_width)
+
+    def keras_weights(self):
+        out = _prefixed("embed_layer", self.embed_layer.keras_weights())
+        out.update(_prefixed("wide", self.wide.keras_weights()))
+        out.update(_prefixed("deep", self.deep.keras_weights()))
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        if not self.wide.built and "wide/w" in weights:
+            self.wide.build(torch.as_tensor(weights["wide/w"]).shape[0])
+        if strict:
+            unknown = set(weights) - set(self.keras_weights())
+            if unknown:
+                raise KeyError(f"unknown weights {sorted(unknown)}")
+        _set_prefixed(self.embed_layer, "embed_layer", weights, strict)
+        _set_prefixed(self.wide, "wide", weights, strict)
+        _set_prefixed(self.deep, "deep", weights, strict)
+        self._weights_changed()
+
+    def _combine(self, wide, ids, check_ids):
+        emb = self.embed_layer.gather(ids, check_ids=check_ids)
+        if self.output_dim == 1 and self.deep.tower_ok():
+            return self.deep.tower(emb, extra=wide, c0=0.5, c1=0.5, head=True)
+        deep = self.deep(emb)
+        return sigmoid_combine(wide.expand(-1, deep.shape[1]).contiguous(), deep, 0.5, 0.5)
+
+    def forward(self, inputs, check_ids=True):
+        X = _packed_f32(inputs, self._dev)
+        nd, F = self.nd, self.embed_layer.n_fields
+        if X.dim() != 2 or X.shape[1] <= nd + F:
+            raise ValueError(f"WideDeep: packed input needs more than {nd + F} columns "
+                             "([dense | codes | dense | dummies])")
+        wide_in = torch.cat([X[:, :nd], X[:, nd + F:]], dim=1)
+        return self._combine(self.wide(wide_in), X[:, nd:nd + F], check_ids)
+
+    def forward_onehot(self, dense, ids, field_offsets, field_widths, check_ids=True):
+        ids = _ids_tensor(ids, self._dev)
+        wide = self.wide.forward_onehot(dense if self.nd else None, ids, field_offsets, field_widths, check_ids)
+        return self._combine(wide, ids, check_ids)
+
+    def train_step(self, *args, **kwargs):
+        raise NotImplementedError("WideDeep.train_step: training WideDeep is not implemented (forward only)")
