@@ -76,7 +76,11 @@ enum rs_option {
   RS_OPT_EMBED_FM_KERNEL = 0, /* rs_embed_fm_fwd kernel (id inputs, no x_out): 0 = MFMA K-split,
                                  1 = VALU/DPP persistent 8-sample tiles, 2 / 3 = MFMA persistent
                                  16-sample tiles (2 / 1 resident per CU); shapes a kernel does
-                                 not cover run the K-split one.  See DESIGN.md 4.1                */
+                                 not cover run the K-split one.  4 / 5 = the K-split kernel, and
+                                 on the host-metadata entries (rs_embed_fm_fwd_hm, _hm_stream) its
+                                 kernarg form: 4 = all arguments in one by-value struct, 5 = the
+                                 hot arguments first, preloaded into SGPRs (0 takes the measured
+                                 default of the two; bit-identical).  See DESIGN.md 4.1           */
   RS_OPT_MLP_UNROLL = 1,      /* fused MLP towers (rs_mlp_fwd, rs_deepfm_fwd, rs_dcn_fwd): 1 (the
                                  default) = the k-group loop of the common layer widths fully
                                  unrolled (no loop-head wait on the weight ring), 0 = the looped
@@ -196,6 +200,13 @@ int rs_embed_gather(const void* ids, int id_kind, int64_t id_stride,
 int64_t rs_fm_prepared_size(int nd, int n_fields, int k, int kfm);
 int rs_fm_prepare(const float* w1, const float* v, int nd, int n_fields, int k,
                   int kfm, float* prepared, rs_stream_t stream);
+/* The kernarg-metadata kernels (below) have instantiations specialised for
+ * one shape, with the packed image's geometry as compile-time constants.
+ * Host-only query of what their launchers decide for a shape: 1 = it is the
+ * specialised shape and the compile-time geometry equals the packed image's
+ * (the specialised kernels run), 0 = another shape, -1 = the shape, but the
+ * geometry differs (both: the generic kernels, run-time geometry).           */
+int rs_embed_fm_ct_geom(int nd, int n_fields, int k, int kfm);
 
 /* Fused EmbedLayer + concat + FMLayer (the headline kernel; DeepFM semantics,
  * model/deepFM.py:24-28).  logit[b] = FMLayer(x)[b]; if x_out != NULL the

@@ -22,6 +22,19 @@ LIB = PKG / "librs_hip.so"
 OBJDIR = PKG / "build"
 ARCH = "gfx950"
 
+# Extra hipcc flags per source (scripts/build_diag.sh and scripts/build_ab.sh
+# mirror this table).
+# embed_fm.hip: leading scalar kernel arguments, 14 dwords at most, arrive in
+# user SGPRs at wave launch instead of through s_loads (the kernarg kernels
+# embed_fm_mfma_kp / embed_fm_stream_kp are laid out for it).  A kernel whose
+# first parameter is a struct is unaffected.  The file's other kernels that
+# start with scalars (fm_prepare_mfma, fm_prepare_generic, the diagnostic
+# probes) keep the flag's effect: it changes only how their first arguments
+# arrive, and they run once per weight set, off the hot path.
+SOURCE_FLAGS = {
+    "embed_fm.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"],
+}
+
 
 def _hipcc() -> str:
     for cand in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
@@ -49,7 +62,7 @@ def _compile(src: Path, hipcc: str, extra) -> Path:
         return obj
     cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
            "-Wno-unused-function", "-I", str(INCLUDE), "-I", str(CSRC), "-c", str(src),
-           "-o", str(obj)] + list(extra)
+           "-o", str(obj)] + SOURCE_FLAGS.get(src.name, []) + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed on {src.name}:\n{r.stdout}\n{r.stderr}")

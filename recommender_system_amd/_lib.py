@@ -44,6 +44,7 @@ SIGNATURES = {
     "rs_embed_gather": (I, [P, I, L, P, L, I, P, P, P, I, I, P, L, L, P, P]),
     "rs_fm_prepared_size": (L, [I, I, I, I]),
     "rs_fm_prepare": (I, [P, P, I, I, I, I, P, P]),
+    "rs_embed_fm_ct_geom": (I, [I, I, I, I]),
     "rs_embed_fm_fwd": (I, [P, I, L, P, L, I, P, P, P, I, I, P, P, I, P, P, L, P, P]),
     "rs_embed_fm_fwd_hm": (I, [P, I, L, P, L, I, P, P, P, P, P, I, I, P, P, I, P, P, L, P, P]),
     "rs_embed_fm_fwd_hm_stream": (I, [P, I, L, L, P, L, L, I, P, P, P, I, I, P, P, I, P, L, L, I, L, I, P, P]),

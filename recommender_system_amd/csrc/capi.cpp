@@ -29,7 +29,7 @@ int launch_status(const char* what) {
 // defaults: K-split headline kernel, unrolled towers, split-role DeepFM, one-launch DIN attention,
 // lean peer-exchange ordering, register contraction in embed_cross
 static thread_local int g_opt[RS_OPT_COUNT] = {0, 1, 0, 0, 0, 0};
-static const int g_opt_hi[RS_OPT_COUNT] = {3, 1, 3, 1, 1, 1};
+static const int g_opt_hi[RS_OPT_COUNT] = {5, 1, 3, 1, 1, 1};
 int opt(int option) { return (option >= 0 && option < RS_OPT_COUNT) ? g_opt[option] : 0; }
 }  // namespace rs
 

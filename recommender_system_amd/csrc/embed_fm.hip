@@ -135,8 +135,9 @@ __global__ void fm_prepare_generic(const float* __restrict__ w1, const float* __
 // FC / KFMC / NDC: the field count, FM width and dense width as compile-time
 // constants (0 / 0 / -1: the kernel arguments' run-time values) — the
 // headline shape's kernarg and streamed kernels take 26 / 10 / 13
+// PL: the caller's hot arguments arrived preloaded in SGPRs (embed_fm_mfma_kp)
 template <int KV, int NT, int NW, int KIND, bool TW, int MC = 0, bool PF = false, bool KA = false, int FC = 0,
-          int KFMC = 0, int NDC = -1>
+          int KFMC = 0, int NDC = -1, bool PL = false>
 __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArgs* tw, const int tile,
                                               const FieldMeta* km = nullptr) {
   const int aF = FC > 0 ? FC : a.F;        // (compile-time at the specialised shapes)
@@ -160,8 +161,9 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
   // row depends only on its own A row, so they never touch valid outputs.
   const int64_t b = bt < a.batch ? bt : a.batch - 1;
   const int d = and_ + aF * a.k;
-  // w0 is requested now, not behind the rows (a dependent load at the end)
-  const float w0v = OWNER ? 0.f : a.w0[0];
+  // w0 is requested now, not behind the rows (a dependent load at the end;
+  // PL: its pointer is a cold argument, so with those — late_args below)
+  float w0v = (OWNER || PL) ? 0.f : a.w0[0];
 
   // four accumulation chains: MFMA tp of a field slot into chain tp & 3,
   // summed below.  Fixed at compile time: the runtime switch this replaced
@@ -182,10 +184,14 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
   // one k-step per wave; wider dense inputs (FMLayer on a plain x) stream.
   // Materialise every kernel argument at entry: one batched s_load instead
   // of lazy per-use kernarg loads (each a dependent K$ round trip).
-  asm volatile("" ::"s"(a.ids), "s"(a.id_stride), "s"(a.dense), "s"(a.dense_stride), "s"(a.nd), "s"(a.table),
-               "s"(a.offs), "s"(a.vocab), "s"(aF), "s"(a.k), "s"(a.prep), "s"(akfm));
-  asm volatile("" ::"s"(a.batch), "s"(a.DB), "s"(a.dense_rec), "s"(a.field_rec), "s"(a.field_base), "s"(a.x_out),
-               "s"(a.logit), "s"(a.w0), "s"(a.err));
+  // (PL: the hot arguments are in SGPRs already and nothing here may wait for
+  // the cold ones — they are materialised behind the id loads, below)
+  if constexpr (!PL) {
+    asm volatile("" ::"s"(a.ids), "s"(a.id_stride), "s"(a.dense), "s"(a.dense_stride), "s"(a.nd), "s"(a.table),
+                 "s"(a.offs), "s"(a.vocab), "s"(aF), "s"(a.k), "s"(a.prep), "s"(akfm));
+    asm volatile("" ::"s"(a.batch), "s"(a.DB), "s"(a.dense_rec), "s"(a.field_rec), "s"(a.field_base), "s"(a.x_out),
+                 "s"(a.logit), "s"(a.w0), "s"(a.err));
+  }
   RS_STAMP(0);
   RS_USE(b);
   RS_STAMP(5);
@@ -424,6 +430,15 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
   // Measured (scripts/ab, profiles/r3_ab_prefetch_*.json): 14.51 vs 15.30 us
   // at batch 16384 (4 tiles per CU), 6.15 vs 6.13 at 4096 (1 tile per CU)
   constexpr bool PRE = PF && KV * MAXC * NT <= 8;
+  // PL: the cold arguments' one batched s_load completes under the id trip —
+  // they are first needed here, behind the B-fragment and id loads (whose
+  // addresses come from preloaded SGPRs and compile-time geometry only)
+  auto late_args = [&]() {
+    if constexpr (PL) {
+      w0v = a.w0[0];
+      asm volatile("" ::"s"(a.k), "s"(a.logit), "s"(a.w0), "s"(a.err));
+    }
+  };
   Pass P0, P1;
   if (PRE) {
     if (has_pass(0)) issue_b(0, P0);
@@ -437,17 +452,22 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
     if (one) {
       // both passes' ids requested together: the second pass's id trip is
       // not serialised behind the first pass's rows and MFMAs (after the B
-      // fragments: ids first was slower, 5.95 vs 5.75 us at 4096)
+      // fragments: ids first was slower, 5.95 vs 5.75 us at 4096, and again
+      // with the arguments preloaded, 5.94 vs 5.63)
       fetch_ids(0, P0);
       if (two) fetch_ids(PS, P1);
     } else if (!coop && aF > 0) {
       load_dense();  // a wave with no field (F < NW) may still own a dense k-step
     }
+    late_args();
     if (one) {
       // (the second pass's rows stay behind the first pass's MFMAs: issuing
       // them with the first pass's was slower, 6.19 vs 5.82 us at 4096 —
       // the r1 finding that two row bursts beat one, again)
       issue_rows(0, P0, true);
+      // (PL: w0, requested in late_args, is taken here, under the row trip —
+      // left alone its load sinks behind the MFMAs, a dependent trip at the end)
+      if constexpr (PL) asm volatile("" ::"s"(w0v));
       norms(P0);
       if (two) norms(P1);
       // the second pass's ids arrive with the first's: its row addresses are
@@ -468,6 +488,7 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
       }
     }
   } else {
+    late_args();
     for (int cg = 0; has_pass(cg); cg += PS) {
       issue_b(cg, P0);
       issue_rows(cg, P0, false);
@@ -589,6 +610,112 @@ __global__ __launch_bounds__(NW * 64) void embed_fm_mfma_ka(EmbedFmArgs a, Field
   embed_fm_body<KV, NT, NW, KIND, false, 1, PF, true, FC, KFMC, NDC>(a, nullptr, blockIdx.x, &m);
 }
 
+// ---- the kernarg kernels with their hot arguments preloaded (RS_OPT_EMBED_FM_KERNEL 5)
+// gfx950 can deliver the leading kernel arguments in user SGPRs at wave
+// launch (this file is compiled with -amdgpu-kernarg-preload-count=14,
+// _build.py), but only leading SCALAR parameters, 14 dwords at most.  So the
+// seven 64-bit values the first B-fragment loads, the id loads and the first
+// row addresses are made of come first, in order of first use, and the rest
+// follows in a by-value struct whose s_loads complete under the id trip.
+// The kernel rebuilds an EmbedFmArgs and runs the same embed_fm_body: the
+// arithmetic, and so every output bit, is the struct-argument kernel's.
+struct EmbedFmCold {
+  float* logit;
+  const float* w0;
+  int* err;
+  int F, k, nd, kfm;
+  const int64_t* offs;
+  const int64_t* vocab;
+  float* x_out;
+  int DB;
+  int64_t dense_rec, field_rec, field_base;
+  int64_t owner_rows;
+  int pw;
+  int64_t pstride;
+  unsigned long long* dbg;
+  int ablate;
+};
+
+static EmbedFmCold cold_args(const EmbedFmArgs& a) {
+  return EmbedFmCold{a.logit, a.w0,        a.err,       a.F,          a.k,          a.nd, a.kfm,     a.offs, a.vocab,
+                     a.x_out, a.DB,        a.dense_rec, a.field_rec,  a.field_base, a.owner_rows,    a.pw,   a.pstride,
+                     a.dbg,   a.ablate};
+}
+
+// The packed image's geometry is a pure function of (nd, F, k, kfm): at a
+// specialised shape (FC > 0) it is fm_geom's value at compile time, so the
+// B-fragment addresses depend on prep and the wave index alone (the launcher
+// checks it against the run-time geometry, ct_geom_matches); the generic
+// instantiations take the run-time values from the cold struct.
+template <int KV, int NT, int FC, int KFMC, int NDC>
+__device__ __forceinline__ EmbedFmArgs hot_cold_args(const float* prep, const void* ids, int64_t id_stride,
+                                                     int64_t batch, const float* dense, int64_t dense_stride,
+                                                     const float* table, const EmbedFmCold& c) {
+  EmbedFmArgs a;
+  a.ids = ids;
+  a.id_stride = id_stride;
+  a.dense = dense;
+  a.dense_stride = dense_stride;
+  a.nd = c.nd;
+  a.table = table;
+  a.offs = c.offs;
+  a.vocab = c.vocab;
+  a.F = c.F;
+  a.k = c.k;
+  a.prep = prep;
+  a.w0 = c.w0;
+  a.kfm = c.kfm;
+  a.logit = c.logit;
+  a.x_out = c.x_out;
+  a.batch = batch;
+  a.err = c.err;
+  if constexpr (FC > 0) {
+    constexpr FmGeom G = fm_geom(NDC, FC, 4 * KV, KFMC);
+    static_assert(G.mfma && G.KV == KV && G.NT == NT, "specialised shape: not this instantiation's geometry");
+    a.DB = G.DB;
+    a.dense_rec = G.dense_rec;
+    a.field_rec = G.field_rec;
+    a.field_base = G.field_base;
+  } else {
+    a.DB = c.DB;
+    a.dense_rec = c.dense_rec;
+    a.field_rec = c.field_rec;
+    a.field_base = c.field_base;
+  }
+  a.owner_rows = c.owner_rows;
+  a.pw = c.pw;
+  a.pstride = c.pstride;
+  a.dbg = c.dbg;
+  a.ablate = c.ablate;
+  return a;
+}
+
+// host side of the same: does the run-time geometry equal the specialised
+// kernels' compile-time one?  (false: the launcher takes the generic kernel)
+template <int KV, int NT, int FC, int KFMC, int NDC>
+static bool ct_geom_matches(const EmbedFmArgs& a) {
+  constexpr FmGeom G = fm_geom(NDC, FC, 4 * KV, KFMC);
+  return G.mfma && G.KV == KV && G.NT == NT && a.F == FC && a.kfm == KFMC && a.nd == NDC && a.k == 4 * KV &&
+         a.DB == G.DB && a.dense_rec == G.dense_rec && a.field_rec == G.field_rec && a.field_base == G.field_base;
+}
+
+// The one specialised shape (Criteo / the headline: 26 fields, FM width 10,
+// 13 dense features, k 16): 1 = this is it and the compile-time geometry
+// holds (the specialised kernels run), 0 = another shape, -1 = the shape but
+// not the geometry (the generic kernels run; rs_embed_fm_ct_geom reports it)
+static int headline_spec(const EmbedFmArgs& a) {
+  if (a.F != 26 || a.kfm != 10 || a.nd != 13 || a.k != 16) return 0;
+  return ct_geom_matches<4, 1, 26, 10, 13>(a) ? 1 : -1;
+}
+
+template <int KV, int NT, int NW, int KIND, bool PF, int FC = 0, int KFMC = 0, int NDC = -1>
+__global__ __launch_bounds__(NW * 64) void embed_fm_mfma_kp(const float* prep, const void* ids, int64_t id_stride,
+                                                            int64_t batch, const float* dense, int64_t dense_stride,
+                                                            const float* table, EmbedFmCold c, FieldMeta m) {
+  const EmbedFmArgs a = hot_cold_args<KV, NT, FC, KFMC, NDC>(prep, ids, id_stride, batch, dense, dense_stride, table, c);
+  embed_fm_body<KV, NT, NW, KIND, false, 1, PF, true, FC, KFMC, NDC, true>(a, nullptr, blockIdx.x, &m);
+}
+
 // S consecutive batches in ONE launch (rs_embed_fm_fwd_hm_stream): workgroup
 // g runs the kernarg kernel's body on tile g % tpb of batch g / tpb (batch-
 // major dispatch order) — the same instantiation and tile arithmetic as the
@@ -611,6 +738,23 @@ __global__ __launch_bounds__(16 * 64, MINB) void embed_fm_stream_ka(EmbedFmArgs 
   if (s == sa.S - 1) b.batch = sa.last_batch;
   if ((int64_t)tile * 16 >= b.batch) return;  // a shorter last batch: fewer tiles (uniform exit)
   embed_fm_body<KV, NT, 16, KIND, false, 1, true, true, FC, KFMC, NDC>(b, nullptr, tile, &m);
+}
+// ... with the hot arguments preloaded (embed_fm_mfma_kp); the batch index
+// and strides are cold, so only the B-fragment loads go out ahead of them
+template <int KV, int NT, int KIND, int MINB, int FC = 0, int KFMC = 0, int NDC = -1>
+__global__ __launch_bounds__(16 * 64, MINB) void embed_fm_stream_kp(const float* prep, const void* ids,
+                                                                    int64_t id_stride, int64_t batch,
+                                                                    const float* dense, int64_t dense_stride,
+                                                                    const float* table, EmbedFmCold c, FieldMeta m,
+                                                                    StreamArgs sa) {
+  const int s = blockIdx.x / sa.tpb, tile = blockIdx.x - s * sa.tpb;
+  EmbedFmArgs b = hot_cold_args<KV, NT, FC, KFMC, NDC>(prep, ids, id_stride, batch, dense, dense_stride, table, c);
+  b.ids = static_cast<const char*>(ids) + s * sa.ids_bstride_bytes;
+  b.dense = dense + s * sa.dense_bstride;
+  b.logit = c.logit + s * sa.logit_bstride;
+  if (s == sa.S - 1) b.batch = sa.last_batch;
+  if ((int64_t)tile * 16 >= b.batch) return;  // a shorter last batch: fewer tiles (uniform exit)
+  embed_fm_body<KV, NT, 16, KIND, false, 1, true, true, FC, KFMC, NDC, true>(b, nullptr, tile, &m);
 }
 
 // ---- sharded FM, partial protocol: combine (requester side) as a block part
@@ -1453,6 +1597,18 @@ static int grid_for(int64_t work, int block, int cap = 2048) {
   return (int)g;
 }
 
+// Which form of the kernarg kernels a launch takes (RS_OPT_EMBED_FM_KERNEL):
+// 4 = EmbedFmArgs by value (embed_fm_mfma_ka / embed_fm_stream_ka), 5 = the
+// hot arguments preloaded (embed_fm_mfma_kp / embed_fm_stream_kp); any other
+// value: the default below, decided by the A/B in DESIGN.md 4.1 (5.97 ->
+// 5.63 us per launch at B 4096, 5.36 -> 4.82 at 2048, bit-identical;
+// profiles/ab_kernarg_preload_{4096,2048}.jsonl).
+constexpr bool kKernargPreloadDefault = true;
+static bool kernarg_preload() {
+  const int v = opt(RS_OPT_EMBED_FM_KERNEL);
+  return v == 5 || (v != 4 && kKernargPreloadDefault);
+}
+
 template <int KV, int NT, int KIND>
 static void launch_embed_fm3(const EmbedFmArgs& a, hipStream_t st, const FieldMeta* hm) {
   // 16 waves per 16-sample tile (measured against 4, 8 and 13 waves), one
@@ -1477,18 +1633,30 @@ static void launch_embed_fm3(const EmbedFmArgs& a, hipStream_t st, const FieldMe
   // 16 waves (13: 6.20 us, 9: 6.78 vs 5.76 at 4096; profiles/r3_ab_kernarg_waves_4096.json)
   // (the kernarg kernel is built lean: at most 2 x 16 fields, 16 dense k-steps,
   // no x output — its straight-line code runs from a cold instruction cache)
-  if (hm && a.F <= 32 && KIND != 3 && grid <= 512 && a.DB <= 16 && !a.x_out) {
-    // (round 5: the ids through 16 scalar loads per wave and a lane select
-    // chain, off the vector memory queue, ran 7.08 vs 6.12 us per launch,
-    // bit-identical — profiles/r5_ab_scalar_ids.json; not kept)
-    if constexpr (KV == 4 && NT == 1 && KIND != 2) {
-      if (a.F == 26 && a.kfm == 10 && a.nd == 13) {  // the Criteo / headline shape
-        embed_fm_mfma_ka<KV, NT, 16, KIND, true, 26, 10, 13><<<grid, 16 * 64, 0, st>>>(a, *hm);
-        return;
+  if constexpr (KIND != 3) {  // (rows already gathered: never the kernarg kernels — none instantiated)
+    if (hm && a.F <= 32 && grid <= 512 && a.DB <= 16 && !a.x_out) {
+      // (round 5: the ids through 16 scalar loads per wave and a lane select
+      // chain, off the vector memory queue, ran 7.08 vs 6.12 us per launch,
+      // bit-identical — profiles/r5_ab_scalar_ids.json; not kept)
+      const bool pl = kernarg_preload();
+      const EmbedFmCold c = cold_args(a);
+      if constexpr (KV == 4 && NT == 1 && KIND != 2) {
+        // the Criteo / headline shape (its compile-time geometry checked: a
+        // mismatch would take the generic kernel, which reads the run-time one)
+        if (headline_spec(a) == 1) {
+          if (pl)
+            embed_fm_mfma_kp<KV, NT, 16, KIND, true, 26, 10, 13><<<grid, 16 * 64, 0, st>>>(
+                a.prep, a.ids, a.id_stride, a.batch, a.dense, a.dense_stride, a.table, c, *hm);
+          else embed_fm_mfma_ka<KV, NT, 16, KIND, true, 26, 10, 13><<<grid, 16 * 64, 0, st>>>(a, *hm);
+          return;
+        }
       }
+      if (pl)
+        embed_fm_mfma_kp<KV, NT, 16, KIND, true><<<grid, 16 * 64, 0, st>>>(a.prep, a.ids, a.id_stride, a.batch, a.dense,
+                                                                           a.dense_stride, a.table, c, *hm);
+      else embed_fm_mfma_ka<KV, NT, 16, KIND, true><<<grid, 16 * 64, 0, st>>>(a, *hm);
+      return;
     }
-    embed_fm_mfma_ka<KV, NT, 16, KIND, true><<<grid, 16 * 64, 0, st>>>(a, *hm);
-    return;
   }
   if (a.F <= 32 && grid > 1024) embed_fm_mfma<KV, NT, 4, KIND, 1, true><<<grid, 4 * 64, 0, st>>>(a);
   else if (a.F <= 32 && grid > 512) embed_fm_mfma<KV, NT, 8, KIND, 1, true><<<grid, 8 * 64, 0, st>>>(a);
@@ -1557,6 +1725,22 @@ using namespace rs;
 extern "C" int64_t rs_fm_prepared_size(int nd, int n_fields, int k, int kfm) {
   if (nd < 0 || n_fields < 0 || kfm < 1 || (n_fields > 0 && k < 1)) return -1;
   return fm_geom(nd, n_fields, k, kfm).size;
+}
+
+extern "C" int rs_embed_fm_ct_geom(int nd, int n_fields, int k, int kfm) {
+  if (nd < 0 || n_fields < 0 || kfm < 1 || (n_fields > 0 && k < 1)) return 0;
+  const FmGeom g = fm_geom(nd, n_fields, k, kfm);
+  if (!g.mfma) return 0;
+  EmbedFmArgs a{};
+  a.nd = nd;
+  a.F = n_fields;
+  a.k = k;
+  a.kfm = kfm;
+  a.DB = g.DB;
+  a.dense_rec = g.dense_rec;
+  a.field_rec = g.field_rec;
+  a.field_base = g.field_base;
+  return headline_spec(a);
 }
 
 extern "C" int rs_fm_prepare(const float* w1, const float* v, int nd, int n_fields, int k, int kfm,
@@ -1715,17 +1899,32 @@ extern "C" int rs_embed_fm_fwd_hm_stream(const void* ids, int id_kind, int64_t i
                 logit_batch_stride, last_batch};
   const unsigned grid = (unsigned)(tpb * n_batches);
   hipStream_t st = as_stream(stream);
+  const bool pl = kernarg_preload();
+  const EmbedFmCold c = cold_args(a);
   auto go = [&](auto kv, auto kind) {
     constexpr int KV = decltype(kv)::value, KIND = decltype(kind)::value;
+    const dim3 gr(grid), bl(16 * 64);
+    // (min_blocks, specialised shape, preloaded hot arguments) -> instantiation
+    auto run = [&](auto mb, auto spec) {
+      constexpr int MB = decltype(mb)::value;
+      constexpr int FC = decltype(spec)::value ? 26 : 0, KC = FC ? 10 : 0, NC = FC ? 13 : -1;
+      if (pl)
+        embed_fm_stream_kp<KV, 1, KIND, MB, FC, KC, NC><<<gr, bl, 0, st>>>(a.prep, a.ids, a.id_stride, a.batch, a.dense,
+                                                                          a.dense_stride, a.table, c, m, sa);
+      else embed_fm_stream_ka<KV, 1, KIND, MB, FC, KC, NC><<<gr, bl, 0, st>>>(a, m, sa);
+    };
+    auto by_mb = [&](auto spec) {
+      if (min_blocks == 2) run(std::integral_constant<int, 2>(), spec);
+      else run(std::integral_constant<int, 1>(), spec);
+    };
     if constexpr (KV == 4) {
-      if (n_fields == 26 && kfm == 10 && nd == 13) {  // the headline shape, as the single launch
-        if (min_blocks == 2) embed_fm_stream_ka<KV, 1, KIND, 2, 26, 10, 13><<<grid, 16 * 64, 0, st>>>(a, m, sa);
-        else embed_fm_stream_ka<KV, 1, KIND, 1, 26, 10, 13><<<grid, 16 * 64, 0, st>>>(a, m, sa);
+      // the headline shape, as the single launch (geometry checked as there)
+      if (headline_spec(a) == 1) {
+        by_mb(std::true_type());
         return;
       }
     }
-    if (min_blocks == 2) embed_fm_stream_ka<KV, 1, KIND, 2><<<grid, 16 * 64, 0, st>>>(a, m, sa);
-    else embed_fm_stream_ka<KV, 1, KIND, 1><<<grid, 16 * 64, 0, st>>>(a, m, sa);
+    by_mb(std::false_type());
   };
   auto by_kind = [&](auto kv) {
     if (id_kind == RS_ID_I64) go(kv, std::integral_constant<int, 1>());

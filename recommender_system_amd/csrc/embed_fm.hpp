@@ -15,7 +15,8 @@ struct FmGeom {
   int64_t dense_rec, field_rec, field_base, size;
 };
 
-static inline FmGeom fm_geom(int nd, int F, int k, int kfm) {
+// (constexpr: the kernels specialised for one shape take it at compile time)
+static inline constexpr FmGeom fm_geom(int nd, int F, int k, int kfm) {
   FmGeom g{};
   g.nd = nd;
   g.F = F;

@@ -4,6 +4,9 @@
 # flags for B in $BFLAGS, for A in $AFLAGS) and, when $CFLAGS is set, the
 # working tree again with those flags as C.  Output: scripts/ab/librs_ab_{A,B,C}.so
 # (diagnostics only; never loaded by the product).
+# The working tree's embed_fm.hip gets the product's per-source flags
+# (recommender_system_amd/_build.py SOURCE_FLAGS: the kernarg preload); A, an
+# older source, gets only what $AFLAGS gives it.
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p scripts/ab
@@ -11,10 +14,17 @@ rm -f scripts/ab/librs_ab_*.so
 A=${1:-}
 if [ -z "$A" ]; then A=$(mktemp -d)/embed_fm.hip; git show HEAD:recommender_system_amd/csrc/embed_fm.hip > "$A"; fi
 C=recommender_system_amd/csrc
-F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -I include -I $C"
-hipcc $F ${AFLAGS:-} "$A" $C/embed_fm_tiles.hip $C/mlp.hip $C/capi.cpp -o scripts/ab/librs_ab_A.so &
-hipcc $F ${BFLAGS:-} $C/embed_fm.hip $C/embed_fm_tiles.hip $C/mlp.hip $C/capi.cpp -o scripts/ab/librs_ab_B.so &
+F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I include -I $C"
+PRELOAD="-mllvm -amdgpu-kernarg-preload-count=14"
+T=$(mktemp -d)
+variant() {  # name, embed_fm source, flags
+  hipcc $F $3 -x hip -c "$2" -o $T/embed_fm_$1.o &&
+    hipcc $F ${3//$PRELOAD/} -shared $T/embed_fm_$1.o $C/embed_fm_tiles.hip $C/mlp.hip $C/capi.cpp -o scripts/ab/librs_ab_$1.so
+}
+variant A "$A" "${AFLAGS:-}" &
+variant B $C/embed_fm.hip "$PRELOAD ${BFLAGS:-}" &
 if [ -n "${CFLAGS:-}" ]; then
-  hipcc $F $CFLAGS $C/embed_fm.hip $C/embed_fm_tiles.hip $C/mlp.hip $C/capi.cpp -o scripts/ab/librs_ab_C.so &
+  variant C $C/embed_fm.hip "$PRELOAD $CFLAGS" &
 fi
 wait
+ls scripts/ab/librs_ab_A.so scripts/ab/librs_ab_B.so > /dev/null

@@ -15,5 +15,6 @@ for src in recommender_system_amd/csrc/*.hip recommender_system_amd/csrc/*.cpp; 
   obj=$O/$(basename $src).o
   if [ ! -f $obj ] || [ $src -nt $obj ] || [ $HDR -nt $obj ]; then echo $src; fi
 done | xargs -r -P 8 -I{} sh -c \
-  'hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -DRS_DIAG_STAMPS -I include -I recommender_system_amd/csrc -c {} -o '"$O"'/$(basename {}).o'
+  'case {} in */embed_fm.hip) X="-mllvm -amdgpu-kernarg-preload-count=14";; *) X="";; esac;  # = _build.py SOURCE_FLAGS
+   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -DRS_DIAG_STAMPS $X -I include -I recommender_system_amd/csrc -c {} -o '"$O"'/$(basename {}).o'
 hipcc --offload-arch=gfx950 -shared -fPIC -o recommender_system_amd/librs_hip_diag.so $O/*.o
