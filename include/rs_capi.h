@@ -663,6 +663,58 @@ int rs_deepcrossing_fwd(const void* ids, int id_kind, int64_t id_stride,
                         int64_t x_last_stride, int64_t batch, int* err_flag,
                         rs_stream_t stream);
 
+/* Training the residual stack (DeepCrossing.train_step).  Every entry takes
+ * exactly the shapes rs_res_tower_ok accepts, launches nothing for batch 0,
+ * is stream-ordered and graph-capturable.
+ * saved (rs_res_tower_saved_size floats, -1 on a bad shape or batch < 0) =
+ *   x_0 [B, d], then unit-major, layer-major, dense row-major a_{u,l}
+ *   [B, N_l]: a_{u,l} = the relu output of hidden layer l (N_l = hidden[l]),
+ *   a_{u,n_hidden} = x_{u+1}, the unit's result (N = d);
+ *   B * (d + n_units * (sum(hidden) + d)) floats.
+ * rs_res_tower_train_fwd / rs_deepcrossing_train_fwd: rs_res_tower_fwd(head
+ * 1) / rs_deepcrossing_fwd, bit-identical, that also store `saved` (x_0 from
+ * the staged tile: in the ids form the only place [dense | rows] is written)
+ * and the head's logit [B]; out [B] = sigmoid(logit).  prepared must hold the
+ * head.
+ * The backward image (rs_res_tower_bwd_prepared_size floats: the forward's
+ * formula for `hidden` reversed, with the head slot) holds, for the units in
+ * the order the backward visits them (last first), chain layer l = W_{n_hidden
+ * - l}^T in the forward's B-fragment layout, no biases, and head_w (NULL =
+ * zeros: an image for the dy form only).  W: n_units * (n_hidden + 1) device
+ * pointers in the forward's order (rs_res_tower_prepare).
+ * rs_res_tower_bwd: one launch over 16-sample tiles.  Exactly one of dy
+ * [B, d] (rows dy_stride apart: dL/dx_U) and g [B] (dL/dx_U = g[b] * head_w)
+ * is given.  deltas = the layout of saved without x_0: delta_{u,l} = dL/d(pre-
+ * activation of layer l of unit u); delta_{u,n_hidden} = dL/dx_{u+1} [x_{u+1}
+ * > 0].  dx0 [B, d] (rows dx0_stride apart) = dL/dx_0.  Masks are
+ * post-activation > 0 (rs_gemm's mask epilogue).  Deterministic; a row's
+ * result does not depend on the batch.                                       */
+int64_t rs_res_tower_saved_size(int d, int n_hidden, const int* hidden,
+                                int n_units, int64_t batch);
+int rs_res_tower_train_fwd(const float* x, int64_t x_stride, int d,
+                           int n_hidden, const int* hidden, int n_units,
+                           const float* prepared, float* saved, float* out,
+                           float* logit, int64_t batch, rs_stream_t stream);
+int rs_deepcrossing_train_fwd(const void* ids, int id_kind, int64_t id_stride,
+                              const float* dense, int64_t dense_stride, int nd,
+                              const float* table, const int64_t* field_offsets,
+                              const int64_t* field_vocab, int n_fields, int k,
+                              int n_hidden, const int* hidden, int n_units,
+                              const float* prepared, float* saved, float* out,
+                              float* logit, int64_t batch, int* err_flag,
+                              rs_stream_t stream);
+int64_t rs_res_tower_bwd_prepared_size(int d, int n_hidden, const int* hidden,
+                                       int n_units);
+int rs_res_tower_prepare_bwd(int d, int n_hidden, const int* hidden,
+                             int n_units, const float* const* W,
+                             const float* head_w, float* prepared,
+                             rs_stream_t stream);
+int rs_res_tower_bwd(const float* saved, int d, int n_hidden,
+                     const int* hidden, int n_units, const float* prepared_bwd,
+                     const float* dy, int64_t dy_stride, const float* g,
+                     float* deltas, float* dx0, int64_t dx0_stride,
+                     int64_t batch, rs_stream_t stream);
+
 /* ------------------------------------------ wide part of Wide&Deep (a17)
  * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
  * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense

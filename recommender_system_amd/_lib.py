@@ -93,7 +93,13 @@ SIGNATURES = {
     "rs_res_tower_prepare": (I, [I, I, P, I, P, P, P, P, P, P]),
     "rs_res_tower_fwd": (I, [P, L, I, I, P, I, P, I, P, L, L, P]),
     "rs_deepcrossing_fwd": (I, [P, I, L, P, L, I, P, P, P, I, I, I, P, I, P, P, P, L, L, P, P]),
-    "rs_wide_onehot_fwd": (I, [P, I, L, P, L, I, P, P, I, P, P, P, L, P, P]),
+    "rs_res_tower_saved_size": (L, [I, I, P, I, L]),
+    "rs_res_tower_train_fwd": (I, [P, L, I, I, P, I, P, P, P, P, L, P]),
+    "rs_deepcrossing_train_fwd": (I, [P, I, L, P, L, I, P, P, P, I, I, I, P, I, P, P, P, P, L, P, P]),
+    "rs_res_tower_bwd_prepared_size": (L, [I, I, P, I]),
+    "rs_res_tower_prepare_bwd": (I, [I, I, P, I, P, P, P, P]),
+    "rs_res_tower_bwd": (I, [P, I, I, P, I, P, P, L, P, P, P, L, L, P]),
+    "rs_wide_onehot_fwd":(I, [P, I, L, P, L, I, P, P, I, P, P, P, L, P, P]),
     "rs_concat_pieces": (I, [I, P, P, P, P, P, P, P, P, L, L, P, P]),
     "rs_deepfm_fused_ok": (I, [I, I, I, I, I, P]),
     "rs_deepfm_fwd": (I, [P, I, L, P, L, I, P, P, P, I, I, P, P, I, I, P, P, P, F, F, P, P, L, P, P]),

@@ -91,6 +91,7 @@ struct ResPrepArgs {
   const float* bias[RES_MAXL];
   ResGeom g;
   float* out;  // the unit's base
+  int trans;   // W[l] is stored [N, K]: pack its transpose (the backward image)
 };
 
 __global__ void res_prepare_unit(ResPrepArgs a) {
@@ -107,7 +108,7 @@ __global__ void res_prepare_unit(ResPrepArgs a) {
     const int64_t blk = r >> 8;
     const int gg = (int)(blk % G), t = (int)(blk / G);
     const int k = 16 * gg + 4 * (lane >> 4) + j, n = 16 * t + (lane & 15);
-    if (k < K && n < N) v = a.W[l][(int64_t)k * N + n];
+    if (k < K && n < N) v = a.trans ? a.W[l][(int64_t)n * K + k] : a.W[l][(int64_t)k * N + n];
   } else {
     int l = 0;
     while (l + 1 < a.g.nl && i >= a.g.boff[l + 1]) ++l;
@@ -120,7 +121,7 @@ __global__ void res_prepare_unit(ResPrepArgs a) {
 __global__ void res_prepare_head(const float* w, const float* b, int d, int dp, float* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= dp + 16) return;
-  out[i] = i < d ? w[i] : (i == dp && b ? b[0] : 0.f);
+  out[i] = i < d ? (w ? w[i] : 0.f) : (i == dp && b ? b[0] : 0.f);
 }
 
 struct ResArgs {
@@ -146,11 +147,17 @@ struct ResArgs {
   float* yh;  // sigmoid(x_L . head_w + head_b) [M], yhs apart (null: no head)
   int64_t yhs;
   int64_t M;
+  // the saved-activation forward (SAVE): every layer's true width, the floats
+  // one sample takes per unit in `saved`, and the head's logit
+  int N[RES_MAXL];
+  int64_t sw;
+  float* saved;
+  float* logit;
 };
 
 // this wave's first item of layer l of unit u: its ring, requested early
-template <int NW>
-__device__ __forceinline__ void res_first_fill(const ResArgs& a, int u, int l, floatx4 (&ring)[MLP_R]) {
+template <int NW, class Args>
+__device__ __forceinline__ void res_first_fill(const Args& a, int u, int l, floatx4 (&ring)[MLP_R]) {
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int T = a.Np[l] >> 4, G = a.Kp[l] >> 4;
@@ -168,7 +175,10 @@ __device__ __forceinline__ floatx4 res_pick(const floatx4 (&s)[RES_SKIP], int i)
   return i == 0 ? s[0] : (i == 1 ? s[1] : (i == 2 ? s[2] : s[3]));
 }
 
-template <int NW, int KIND>
+// SAVE: the training forward — the finishing thread also stores every layer's
+// post-activation output (and the staging thread the input tile) to a.saved =
+// x_0 [M, d] | unit-major, layer-major a_{u,l} [M, N_l], and the head its logit
+template <int NW, int KIND, bool SAVE = false>
 __global__ __launch_bounds__(NW * 64) void res_tower(ResArgs a) {
   extern __shared__ float smem[];
   const int RS = a.rs;
@@ -185,7 +195,13 @@ __global__ __launch_bounds__(NW * 64) void res_tower(ResArgs a) {
     const int64_t m = m0 + r < a.M ? m0 + r : a.M - 1;
     if constexpr (KIND == 3) {
       const float* xr = a.x + m * a.xs;
-      for (int c = lane; c < a.dp; c += 64) smem[r * RS + c] = c < a.d ? xr[c] : 0.f;
+      for (int c = lane; c < a.dp; c += 64) {
+        const float v = c < a.d ? xr[c] : 0.f;
+        smem[r * RS + c] = v;
+        if constexpr (SAVE) {
+          if (m0 + r < a.M && c < a.d) a.saved[m * a.d + c] = v;
+        }
+      }
     } else {
       typedef Ids<KIND> I;
       bool bad = false;
@@ -201,6 +217,9 @@ __global__ __launch_bounds__(NW * 64) void res_tower(ResArgs a) {
           bad |= !ok;
         }
         smem[r * RS + c] = v;
+        if constexpr (SAVE) {
+          if (m0 + r < a.M && c < a.d) a.saved[m * a.d + c] = v;
+        }
       }
       if (__any(bad) && lane == 0) flag_error(a.err);
     }
@@ -219,6 +238,7 @@ __global__ __launch_bounds__(NW * 64) void res_tower(ResArgs a) {
     floatx4 skip[RES_SKIP];
 #pragma unroll
     for (int i = 0; i < RES_SKIP; ++i) skip[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    int64_t spre = a.d + u * a.sw;  // SAVE: floats per sample before a_{u,l}
     for (int l = 0; l < a.nl; ++l) {
       const int T = a.Np[l] >> 4, G = a.Kp[l] >> 4;
       const int S = mlp_slices(T, G, NW);
@@ -245,14 +265,25 @@ __global__ __launch_bounds__(NW * 64) void res_tower(ResArgs a) {
       const bool last = l == LL;
       // one finished element: hidden layers relu(v + b); the unit's last layer
       // relu(x_u + (v + b)), also to x_L when this is the last unit
+      const int Nl = SAVE ? a.N[l] : 0;
+      float* sv = SAVE ? a.saved + a.M * spre : nullptr;  // a_{u,l} [M, Nl]
+      spre += Nl;
       auto finish = [&](int row, int col, float v, float bc, float sk) {
         if (!last) {
-          out[row * RS + col] = fmaxf(v + bc, 0.f);
+          const float y = fmaxf(v + bc, 0.f);
+          out[row * RS + col] = y;
+          if constexpr (SAVE) {
+            const int64_t m = m0 + row;
+            if (m < a.M && col < Nl) sv[m * Nl + col] = y;
+          }
         } else {
           const float y = fmaxf(sk + (v + bc), 0.f);
           out[row * RS + col] = y;
           const int64_t m = m0 + row;
           if (final_unit && a.xl && m < a.M && col < a.d) a.xl[m * a.xls + col] = y;
+          if constexpr (SAVE) {
+            if (m < a.M && col < Nl) sv[m * Nl + col] = y;
+          }
         }
       };
 
@@ -304,7 +335,10 @@ __global__ __launch_bounds__(NW * 64) void res_tower(ResArgs a) {
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
       const int64_t m = m0 + r;
-      if (lane == 0 && m < a.M) a.yh[m * a.yhs] = sigmoidf_(z + hw[a.dp]);
+      if (lane == 0 && m < a.M) {
+        a.yh[m * a.yhs] = sigmoidf_(z + hw[a.dp]);
+        if constexpr (SAVE) a.logit[m] = z + hw[a.dp];
+      }
     }
   }
 }
@@ -327,14 +361,196 @@ static void res_fill_args(const ResGeom& g, const float* prepared, ResArgs& a) {
   a.unroll = opt(RS_OPT_MLP_UNROLL);
 }
 
-template <int KIND>
+template <int KIND, bool SAVE = false>
 static int res_launch(const ResArgs& a, const ResGeom& g, rs_stream_t stream, const char* what) {
   const int64_t grid = (a.M + 15) / 16;
   RS_REQUIRE(grid < (1ll << 31), "%s: batch too large", what);
   static LdsAttr lds_set;
-  lds_attr(lds_set, (const void*)res_tower<RES_NW, KIND>, g.lds);
-  res_tower<RES_NW, KIND><<<(unsigned)grid, RES_NW * 64, g.lds, as_stream(stream)>>>(a);
+  lds_attr(lds_set, (const void*)res_tower<RES_NW, KIND, SAVE>, g.lds);
+  res_tower<RES_NW, KIND, SAVE><<<(unsigned)grid, RES_NW * 64, g.lds, as_stream(stream)>>>(a);
   return launch_status(what);
+}
+
+// ---- Training.  The floats one sample takes per unit in `saved` / `deltas`
+// (sum of the hidden widths + d) and the offset of layer l inside them.
+struct ResSaved {
+  int N[RES_MAXL];
+  int64_t pre[RES_MAXL], sw;
+};
+static ResSaved res_saved(int d, int n_hidden, const int* hidden) {
+  ResSaved s{};
+  for (int l = 0; l <= n_hidden; ++l) {
+    s.N[l] = l == n_hidden ? d : hidden[l];
+    s.pre[l] = s.sw;
+    s.sw += s.N[l];
+  }
+  return s;
+}
+// the geometry of a unit's backward chain: the forward's with `hidden` reversed
+static bool res_geom_bwd(int d, int n_hidden, const int* hidden, int n_units, ResGeom& g) {
+  if (n_hidden < 1 || n_hidden > RES_MAXH || !hidden) return false;
+  int rev[RES_MAXH];
+  for (int l = 0; l < n_hidden; ++l) rev[l] = hidden[n_hidden - 1 - l];
+  return res_geom(d, n_hidden, rev, n_units, 1, g);
+}
+
+// The backward data path of the stack, the forward's launch shape run in
+// reverse: image unit i is forward unit u = U-1-i, its chain layer l is
+// W_{n_hidden - l}^T (rs_res_tower_prepare_bwd), so the widths are the
+// forward's reversed and the last chain layer is d wide again.
+//   * Staging: e_u = dy_u [x_{u+1} > 0] for the top unit (dy, or g[b] head_w
+//     in the head form), stored as delta_{u,n_hidden}.  It is the first chain
+//     layer's input tile AND the skip operand, held in registers exactly as
+//     the forward holds x_u.
+//   * A hidden step finishes delta_{u,j} = (delta_{u,j+1} W_{j+1}^T) [a_{u,j}
+//     > 0]: the mask value comes from `saved`, loaded by the finishing lane
+//     over the contraction (where the forward loads the bias).
+//   * The d-wide step finishes dy_{u-1} = e_u + delta_{u,0} W_0^T, masked
+//     with [x_u > 0] into delta_{u-1,n_hidden} (the next unit's e, left in
+//     LDS), or unmasked into dx0 for u = 0.
+// Padded columns come out as exact zeros (zero packed weights, zero mask),
+// rows past M are computed from row M-1's staging and never stored.
+struct ResBwdArgs {
+  const float* saved;  // x_0 [M, d] | a_{u,l} [M, N_l]
+  const float* dy;     // dL/dx_U [M, d], rows dys apart, or null:
+  int64_t dys;
+  const float* g;      // ... dL/dx_U = g[m] * head_w (the image's head slot)
+  float* deltas;       // delta_{u,l} [M, N_l], the layout of saved without x_0
+  float* dx0;          // [M, d], rows dx0s apart
+  int64_t dx0s;
+  const float* prep;
+  int d, dp, nl, n_units, rs, unroll;
+  int Kp[RES_MAXL], Np[RES_MAXL];  // of the chain (reversed widths)
+  int64_t off[RES_MAXL], unit, head_off;
+  int fN[RES_MAXL];       // forward layer widths
+  int64_t fpre[RES_MAXL], sw;
+  int64_t M;
+};
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void res_tower_bwd(ResBwdArgs a) {
+  extern __shared__ float smem[];
+  const int RS = a.rs;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t m0 = (int64_t)blockIdx.x * 16;
+  const int nh = a.nl - 1, U = a.n_units;
+  const float* sv = a.saved + a.M * a.d;  // a_{u,l} at sv + M (u sw + fpre[l]), as delta_{u,l} in deltas
+
+  floatx4 ring[MLP_R];
+  res_first_fill<NW>(a, 0, 0, ring);
+  {
+    const int64_t top = a.M * ((U - 1) * a.sw + a.fpre[nh]);
+    const float* hw = a.prep + a.head_off;
+    for (int r = w; r < 16; r += NW) {
+      const bool live = m0 + r < a.M;
+      const int64_t m = live ? m0 + r : a.M - 1;
+      const float gm = a.g ? a.g[m] : 0.f;
+      for (int c = lane; c < a.dp; c += 64) {
+        float v = 0.f;
+        if (c < a.d) {
+          const float dyv = a.g ? gm * hw[c] : a.dy[m * a.dys + c];
+          v = sv[top + m * a.d + c] > 0.f ? dyv : 0.f;
+          if (live) a.deltas[top + m * a.d + c] = v;
+        }
+        smem[r * RS + c] = v;
+      }
+    }
+  }
+
+  float* in = smem;
+  float* out = smem + 16 * RS;
+  float* red = smem + 32 * RS;
+  const int LL = a.nl - 1;
+  const int TL = a.Np[LL] >> 4;
+  const int SL = mlp_slices(TL, a.Kp[LL] >> 4, NW);
+  for (int i = 0; i < U; ++i) {
+    const int u = U - 1 - i;
+    const float* up = a.prep + i * a.unit;
+    floatx4 skip[RES_SKIP];
+#pragma unroll
+    for (int q = 0; q < RES_SKIP; ++q) skip[q] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int l = 0; l < a.nl; ++l) {
+      const int T = a.Np[l] >> 4, G = a.Kp[l] >> 4;
+      const int S = mlp_slices(T, G, NW);
+      __syncthreads();  // the layer's input complete
+      if (l == 0) {
+        // e_u, by the thread that will add it back
+        if (SL == 1) {
+#pragma unroll
+          for (int q = 0; q < RES_SKIP; ++q) {
+            const int t = w + NW * q;
+            if (t < TL) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) skip[q][r] = in[(4 * (lane >> 4) + r) * RS + 16 * t + (lane & 15)];
+            }
+          }
+        } else if ((int)threadIdx.x < TL * 256) {
+          const int e = threadIdx.x, t = e >> 8, ln = (e & 255) >> 2, r = e & 3;
+          skip[0][0] = in[(4 * (ln >> 4) + r) * RS + 16 * t + (ln & 15)];
+        }
+      }
+      const floatx4* W = reinterpret_cast<const floatx4*>(up + a.off[l]) + lane;
+      const bool last = l == LL;
+      // what this step finishes: delta_{u,nh-1-l}, or (last) delta_{u-1,nh} / dx0
+      const bool masked = !(last && u == 0);
+      const int No = last ? a.d : a.fN[nh - 1 - l];
+      const int64_t ob = !masked ? 0 : a.M * (last ? (u - 1) * a.sw + a.fpre[nh] : u * a.sw + a.fpre[nh - 1 - l]);
+      const float* mp = sv + ob;
+      float* dst = masked ? a.deltas + ob : a.dx0;
+      const int64_t ds = masked ? No : a.dx0s;
+      auto mask_at = [&](int row, int col) {
+        const int64_t m = m0 + row;
+        return (masked && m < a.M && col < No) ? mp[m * No + col] : 0.f;
+      };
+      auto finish = [&](int row, int col, float v, float mk, float sk) {
+        float y = last ? sk + v : v;
+        if (masked) y = mk > 0.f ? y : 0.f;
+        out[row * RS + col] = y;
+        const int64_t m = m0 + row;
+        if (m < a.M && col < No) dst[m * ds + col] = y;
+      };
+
+      const float* ap = in + (lane & 15) * RS + 4 * (lane >> 4);
+      int q = 0;
+      for (int item = w; item < T * S; item += NW, ++q) {
+        const MlpItem it = mlp_item(item, T, G, S);
+        const floatx4* bp = W + (int64_t)it.t * G * 64;
+        if (item != w) mlp_ring_fill(ring, bp, it.g0, it.g1);
+        const int col = 16 * it.t + (lane & 15);
+        float mk[4] = {0.f, 0.f, 0.f, 0.f};
+        if (S == 1) {  // in flight over the contraction
+#pragma unroll
+          for (int r = 0; r < 4; ++r) mk[r] = mask_at(4 * (lane >> 4) + r, col);
+        }
+        floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+        mlp_mac(ring, ap, bp, it.g0, it.g1, acc, a.unroll);
+        if (S == 1) {
+          const floatx4 sk = res_pick(skip, q);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) finish(4 * (lane >> 4) + r, col, acc[r], mk[r], sk[r]);
+        } else {
+          *reinterpret_cast<floatx4*>(red + item * 256 + lane * 4) = acc;
+        }
+      }
+      if (l + 1 < a.nl) res_first_fill<NW>(a, i, l + 1, ring);
+      else if (i + 1 < U) res_first_fill<NW>(a, i + 1, 0, ring);
+      if (S > 1) {
+        __syncthreads();  // the partial tiles in red
+        for (int e = threadIdx.x; e < T * 256; e += NW * 64) {
+          const int t = e >> 8, q2 = e & 255, ln = q2 >> 2, r = q2 & 3;
+          const int row = 4 * (ln >> 4) + r, col = 16 * t + (ln & 15);
+          const float mk = mask_at(row, col);
+          float v = 0.f;
+          for (int p = 0; p < S; ++p) v += red[(p * T + t) * 256 + q2];
+          finish(row, col, v, mk, skip[0][0]);
+        }
+      }
+      float* tmp = in;
+      in = out;
+      out = tmp;
+    }
+  }
 }
 
 }  // namespace rs
@@ -449,4 +665,166 @@ extern "C" int rs_deepcrossing_fwd(const void* ids, int id_kind, int64_t id_stri
   int st = RS_OK;
   with_id_kind(id_kind, [&](auto K) { st = res_launch<decltype(K)::value>(a, g, stream, "rs_deepcrossing_fwd"); });
   return st;
+}
+
+// ------------------------------------------------------------------ training
+extern "C" int64_t rs_res_tower_saved_size(int d, int n_hidden, const int* hidden, int n_units, int64_t batch) {
+  ResGeom g;
+  if (!res_geom(d, n_hidden, hidden, n_units, 1, g) || batch < 0) {
+    set_error("rs_res_tower_saved_size: " RES_SHAPE_MSG ", batch >= 0", RES_MAXH, RES_MAXU, MLP_MAXD);
+    return -1;
+  }
+  return batch * (d + n_units * res_saved(d, n_hidden, hidden).sw);
+}
+
+static void res_fill_saved(int d, int n_hidden, const int* hidden, float* saved, float* logit, ResArgs& a) {
+  const ResSaved s = res_saved(d, n_hidden, hidden);
+  for (int l = 0; l <= n_hidden; ++l) a.N[l] = s.N[l];
+  a.sw = s.sw;
+  a.saved = saved;
+  a.logit = logit;
+}
+
+extern "C" int rs_res_tower_train_fwd(const float* x, int64_t x_stride, int d, int n_hidden, const int* hidden,
+                                      int n_units, const float* prepared, float* saved, float* out, float* logit,
+                                      int64_t batch, rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  ResGeom g;
+  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, 1, g), "rs_res_tower_train_fwd: " RES_SHAPE_MSG, RES_MAXH,
+             RES_MAXU, MLP_MAXD);
+  RS_REQUIRE(x && prepared && saved && out && logit, "rs_res_tower_train_fwd: null pointer");
+  RS_REQUIRE(batch >= 0 && x_stride >= d, "rs_res_tower_train_fwd: bad batch/stride (x_stride < d)");
+  ResArgs a{};
+  res_fill_args(g, prepared, a);
+  res_fill_saved(d, n_hidden, hidden, saved, logit, a);
+  a.x = x;
+  a.xs = x_stride;
+  a.yh = out;
+  a.yhs = 1;
+  a.M = batch;
+  return res_launch<3, true>(a, g, stream, "rs_res_tower_train_fwd");
+}
+
+extern "C" int rs_deepcrossing_train_fwd(const void* ids, int id_kind, int64_t id_stride, const float* dense,
+                                         int64_t dense_stride, int nd, const float* table,
+                                         const int64_t* field_offsets, const int64_t* field_vocab, int n_fields,
+                                         int k, int n_hidden, const int* hidden, int n_units, const float* prepared,
+                                         float* saved, float* out, float* logit, int64_t batch, int* err_flag,
+                                         rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  RS_REQUIRE(batch >= 0 && nd >= 0 && n_fields >= 1 && k >= 1 && n_fields <= MLP_MAXD && k <= MLP_MAXD,
+             "rs_deepcrossing_train_fwd: bad shape");
+  const int d = nd + n_fields * k;
+  ResGeom g;
+  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, 1, g),
+             "rs_deepcrossing_train_fwd: " RES_SHAPE_MSG " (input width nd + n_fields * k)", RES_MAXH, RES_MAXU,
+             MLP_MAXD);
+  RS_REQUIRE(ids && table && field_offsets && field_vocab && prepared && saved && out && logit && (nd == 0 || dense),
+             "rs_deepcrossing_train_fwd: null pointer");
+  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_deepcrossing_train_fwd: bad id_kind");
+  RS_REQUIRE(id_stride >= n_fields && (nd == 0 || dense_stride >= nd),
+             "rs_deepcrossing_train_fwd: id_stride / dense_stride smaller than the width");
+  RS_REQUIRE((uintptr_t)table % 16 == 0, "rs_deepcrossing_train_fwd: table must be 16-B aligned");
+  ResArgs a{};
+  res_fill_args(g, prepared, a);
+  res_fill_saved(d, n_hidden, hidden, saved, logit, a);
+  a.ids = ids;
+  a.id_stride = id_stride;
+  a.dense = dense;
+  a.dense_stride = dense_stride;
+  a.nd = nd;
+  a.table = table;
+  a.offs = field_offsets;
+  a.vocab = field_vocab;
+  a.F = n_fields;
+  a.k = k;
+  a.err = err_flag;
+  a.yh = out;
+  a.yhs = 1;
+  a.M = batch;
+  int st = RS_OK;
+  with_id_kind(id_kind, [&](auto K) {
+    st = res_launch<decltype(K)::value, true>(a, g, stream, "rs_deepcrossing_train_fwd");
+  });
+  return st;
+}
+
+extern "C" int64_t rs_res_tower_bwd_prepared_size(int d, int n_hidden, const int* hidden, int n_units) {
+  ResGeom g;
+  if (!res_geom_bwd(d, n_hidden, hidden, n_units, g)) {
+    set_error("rs_res_tower_bwd_prepared_size: " RES_SHAPE_MSG, RES_MAXH, RES_MAXU, MLP_MAXD);
+    return -1;
+  }
+  return g.total;
+}
+
+extern "C" int rs_res_tower_prepare_bwd(int d, int n_hidden, const int* hidden, int n_units, const float* const* W,
+                                        const float* head_w, float* prepared, rs_stream_t stream) {
+  ResGeom g;
+  RS_REQUIRE(res_geom_bwd(d, n_hidden, hidden, n_units, g), "rs_res_tower_prepare_bwd: " RES_SHAPE_MSG, RES_MAXH,
+             RES_MAXU, MLP_MAXD);
+  RS_REQUIRE(W && prepared, "rs_res_tower_prepare_bwd: null pointer");
+  for (int i = 0; i < n_units * g.nl; ++i)
+    RS_REQUIRE(W[i], "rs_res_tower_prepare_bwd: unit %d layer %d has no kernel", i / g.nl, i % g.nl);
+  for (int i = 0; i < n_units; ++i) {
+    // image unit i = forward unit n_units-1-i; chain layer l = W_{n_hidden-l}^T; no biases
+    ResPrepArgs a{};
+    for (int l = 0; l < g.nl; ++l) a.W[l] = W[(n_units - 1 - i) * g.nl + (n_hidden - l)];
+    a.g = g;
+    a.out = prepared + i * g.unit;
+    a.trans = 1;
+    res_prepare_unit<<<(unsigned)((g.unit + 255) / 256), 256, 0, as_stream(stream)>>>(a);
+  }
+  // the head slot is always there (head_w NULL: zeros, an image for the dy form only)
+  res_prepare_head<<<(g.dp + 16 + 255) / 256, 256, 0, as_stream(stream)>>>(head_w, nullptr, g.d, g.dp,
+                                                                         prepared + g.head_off);
+  return launch_status("rs_res_tower_prepare_bwd");
+}
+
+extern "C" int rs_res_tower_bwd(const float* saved, int d, int n_hidden, const int* hidden, int n_units,
+                                const float* prepared_bwd, const float* dy, int64_t dy_stride, const float* g,
+                                float* deltas, float* dx0, int64_t dx0_stride, int64_t batch, rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  ResGeom gm;
+  RS_REQUIRE(res_geom_bwd(d, n_hidden, hidden, n_units, gm), "rs_res_tower_bwd: " RES_SHAPE_MSG, RES_MAXH, RES_MAXU,
+             MLP_MAXD);
+  RS_REQUIRE(saved && prepared_bwd && deltas && dx0, "rs_res_tower_bwd: null pointer");
+  RS_REQUIRE((dy != nullptr) != (g != nullptr), "rs_res_tower_bwd: exactly one of dy and g");
+  RS_REQUIRE(batch >= 0 && dx0_stride >= d && (!dy || dy_stride >= d),
+             "rs_res_tower_bwd: bad batch/stride (dy_stride or dx0_stride < d)");
+  const int64_t grid = (batch + 15) / 16;
+  RS_REQUIRE(grid < (1ll << 31), "rs_res_tower_bwd: batch too large");
+  ResBwdArgs a{};
+  for (int l = 0; l < gm.nl; ++l) {
+    a.Kp[l] = gm.Kp[l];
+    a.Np[l] = gm.Np[l];
+    a.off[l] = gm.off[l];
+  }
+  const ResSaved s = res_saved(d, n_hidden, hidden);
+  for (int l = 0; l <= n_hidden; ++l) {
+    a.fN[l] = s.N[l];
+    a.fpre[l] = s.pre[l];
+  }
+  a.sw = s.sw;
+  a.saved = saved;
+  a.dy = dy;
+  a.dys = dy_stride;
+  a.g = g;
+  a.deltas = deltas;
+  a.dx0 = dx0;
+  a.dx0s = dx0_stride;
+  a.prep = prepared_bwd;
+  a.d = gm.d;
+  a.dp = gm.dp;
+  a.nl = gm.nl;
+  a.n_units = gm.n_units;
+  a.rs = gm.rs;
+  a.unit = gm.unit;
+  a.head_off = gm.head_off;
+  a.unroll = opt(RS_OPT_MLP_UNROLL);
+  a.M = batch;
+  static LdsAttr lds_set;
+  lds_attr(lds_set, (const void*)res_tower_bwd<RES_NW>, gm.lds);
+  res_tower_bwd<RES_NW><<<(unsigned)grid, RES_NW * 64, gm.lds, as_stream(stream)>>>(a);
+  return launch_status("rs_res_tower_bwd");
 }

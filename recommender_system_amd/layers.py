@@ -1304,8 +1304,9 @@ class WideLayer(KerasModule):
     (model/wideDeep.py:22-27) and gathers one scalar of w per field
     (rs_wide_onehot_fwd) instead of multiplying by zeros."""
 
-    def __init__(self, device=None, seed=None):
+    def __init__(self, device=None, seed=None, w_reg=1e-4):
         super().__init__(device, seed)
+        self.w_reg = float(w_reg)  # l2 on w (layer/interaction.py:22); training only
         self.w0 = self.w = None
 
     @property

@@ -1475,7 +1475,8 @@ class DeepCrossing(KerasModule):
     concat is never written, every activation stays in LDS);
     ``forward_unfused`` is the gather, one launch per unit (or the per-layer
     composition where the tower kernel does not take the shape), then the
-    Dense + sigmoid.  ``forward`` takes the fused path when ``fused_ok()``."""
+    Dense + sigmoid.  ``forward`` takes the fused path when ``fused_ok()``.
+    ``train_step`` is one step of compile_fit (model/deepCrossing.py:45)."""
 
     def __init__(self, feature_columns, k, hidden_units, res_layer_num, embed_dim=8, device=None, seed=None):
         super().__init__(device, seed)
@@ -1512,6 +1513,7 @@ class DeepCrossing(KerasModule):
 
     def _invalidate(self):
         self.__dict__.pop("_res_prep", None)
+        self.__dict__.pop("_res_prep_bwd", None)
 
     def _all_layers(self):
         return [l for unit in self.res_layer for l in unit._layers()] + [self.output_layer]
@@ -1560,8 +1562,126 @@ class DeepCrossing(KerasModule):
             return self.forward_fused(inputs, check_ids)
         return self.forward_unfused(inputs, check_ids)
 
-    def train_step(self, *args, **kwargs):
-        raise NotImplementedError("DeepCrossing.train_step: training DeepCrossing is not implemented (forward only)")
+    def prepared_bwd(self):
+        """The backward weight image (rs_res_tower_prepare_bwd: every unit's
+        kernels transposed, last unit first, and the head's kernel), cached
+        under the key of ``prepared``."""
+        key = _res_key(self._all_layers())
+        ent = self.__dict__.get("_res_prep_bwd")
+        if ent is None or ent[0] != key:
+            nh, nu = len(self.hidden_units), len(self.res_layer)
+            ci = (C.c_int * nh)(*self.hidden_units)
+            size = _lib.lib().rs_res_tower_bwd_prepared_size(self.d, nh, ci, nu)
+            if size < 0:
+                _lib.check(-1, "rs_res_tower_bwd_prepared_size")
+            kernels = [l.kernel for l in self._all_layers()[:-1]]
+            img = torch.empty(size, dtype=torch.float32, device=self._dev)
+            call("rs_res_tower_prepare_bwd", self.d, nh, ci, nu,
+                 (C.c_void_p * len(kernels))(*[ptr(t) for t in kernels]), ptr(self.output_layer.kernel), ptr(img),
+                 _lib.stream())
+            ent = self.__dict__["_res_prep_bwd"] = (key, img)
+        return ent[1]
+
+    def train_step(self, inputs, labels, lr=0.01, return_loss=False, check_ids=True, fused=None):
+        """One step of compile_fit (utils/compile_fit.py:9-15: SGD(lr), binary
+        cross-entropy on the sigmoid head; model/deepCrossing.py:45 — the model
+        has no regulariser, Dropout or BN), every weight updated in place.
+
+        ``fused=True``: the forward with saved activations from the ids in one
+        launch (rs_deepcrossing_train_fwd), rs_head_grad, the whole backward
+        data path in one launch (rs_res_tower_bwd: every layer's delta and
+        dL/dx_0).  ``fused=False``: rs_embed_gather, rs_dense_fwd per layer
+        with a torch add / relu per unit, and _dnn_backward per unit with a
+        torch mask / add at the joins.  Both then take the weight gradients
+        from the same deterministic blocks (rs_gemm(trans_a) + rs_col_sum per
+        layer), one rs_sgd_update_multi and the row-sparse rs_embedding_sgd.
+        ``None`` picks fused when ``fused_ok()``; ``True`` raises where the
+        kernels do not take the shape.  A bad id raises IndexError before any
+        weight changes (``check_ids``).  Returns the per-sample losses before
+        the step if ``return_loss``."""
+        if self._dev.type != "cuda":
+            raise NotImplementedError("DeepCrossing.train_step: training runs only on a HIP device")
+        if fused is None:
+            fused = self.fused_ok()
+        elif fused and not self.fused_ok():
+            raise ValueError("DeepCrossing.train_step(fused=True): the residual tower kernels do not take this shape")
+        dense, ids = _split_criteo(inputs, self.nd, self._dev)
+        labels = _to_device_f32(labels, self._dev).reshape(-1)
+        e, head = self.embed_layer, self.output_layer
+        units = [u._layers() for u in self.res_layer]
+        B, d, st, dev = ids.shape[0], self.d, _lib.stream(), self._dev
+        nh, nu = len(self.hidden_units), len(units)
+        emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        all_layers = self._all_layers()
+        gws = _gemm_ws(self, max(_lib.lib().rs_gemm_workspace_size(L.kernel.shape[0], L.kernel.shape[1], B)
+                                 for L in all_layers))
+        gw = (ptr(gws), gws.numel())
+        g, g0 = emp(B), emp(B)
+        loss = emp(B) if return_loss else None
+        if fused:
+            ci = (C.c_int * nh)(*self.hidden_units)
+            widths = self.hidden_units + [d]
+            saved = emp(B * (d + nu * sum(widths)))
+            deltas = emp(B * nu * sum(widths))
+            prob, logit, dx0 = emp(B), emp(B), emp(B, d)
+            call("rs_deepcrossing_train_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0),
+                 ptr(dense) if self.nd else None, dense.stride(0) if self.nd else 0, self.nd, ptr(e.table),
+                 ptr(e.field_offsets), ptr(e.field_vocab), e.n_fields, e.k, nh, ci, nu, ptr(self.prepared()),
+                 ptr(saved), ptr(prob), ptr(logit), B, ptr(self._err.t), st)
+            if check_ids:
+                self._err.check("DeepCrossing.train_step")
+            call("rs_head_grad", ptr(logit), ptr(logit), ptr(labels), B, 1.0, 0.0, ptr(g), ptr(g0), ptr(loss), st)
+            call("rs_res_tower_bwd", ptr(saved), d, nh, ci, nu, ptr(self.prepared_bwd()), None, 0, ptr(g),
+                 ptr(deltas), ptr(dx0), d, B, st)
+            # views of saved / deltas: x_u and a_{u,l}, delta_{u,l}
+            xs, acts, dels, so, do = [saved[:B * d].view(B, d)], [], [], B * d, 0
+            for u in range(nu):
+                au, du = [], []
+                for n in widths:
+                    au.append(saved[so:so + B * n].view(B, n))
+                    du.append(deltas[do:do + B * n].view(B, n))
+                    so, do = so + B * n, do + B * n
+                acts.append(au)
+                dels.append(du)
+                xs.append(au[-1])
+            grads = []
+            for u, layers in enumerate(units):
+                for l, L in enumerate(layers):
+                    a_in, dl = (xs[u] if l == 0 else acts[u][l - 1]), dels[u][l]
+                    K_in, N_out = L.kernel.shape
+                    dW, db = emp(K_in, N_out), emp(N_out)
+                    call("rs_gemm", 1, 0, K_in, N_out, B, 1.0, ptr(a_in), a_in.stride(0), ptr(dl), dl.stride(0), 0.0,
+                         ptr(dW), N_out, None, 0, *gw, st)
+                    call("rs_col_sum", ptr(dl), dl.stride(0), B, N_out, ptr(db), st)
+                    grads.append((L, dW, db))
+            dWh, dbh = emp(d, 1), emp(1)
+            call("rs_gemm", 1, 0, d, 1, B, 1.0, ptr(xs[nu]), d, ptr(g), 1, 0.0, ptr(dWh), 1, None, 0, *gw, st)
+            call("rs_col_sum", ptr(g), 1, B, 1, ptr(dbh), st)
+            grads.append((head, dWh, dbh))
+        else:
+            x = e.gather(ids, dense if self.nd else None, check_ids=check_ids)
+            xs, acts = [x], []
+            for layers in units:
+                au = [xs[-1]]
+                for L in layers[:-1]:
+                    au.append(L(au[-1]))
+                xs.append(torch.relu(xs[-1] + layers[-1](au[-1])))
+                acts.append(au)
+            logit = emp(B)
+            call("rs_dense_fwd", ptr(xs[-1]), xs[-1].stride(0), ptr(head.kernel), ptr(head.bias), None, _lib.ACT[None],
+                 ptr(logit), 1, B, d, 1, st)
+            call("rs_head_grad", ptr(logit), ptr(logit), ptr(labels), B, 1.0, 0.0, ptr(g), ptr(g0), ptr(loss), st)
+            grads, dy = _dnn_backward([head], [xs[-1]], g.view(B, 1), gw, emp, st)
+            for u in reversed(range(nu)):
+                eu = dy * (xs[u + 1] > 0)
+                gu, below = _dnn_backward(units[u], acts[u], eu, gw, emp, st)
+                grads = gu + grads
+                dy = eu + below
+            dx0 = dy
+        _dnn_apply(grads, lr, st)
+        _embedding_sgd(self, ids, dx0, dx0.stride(0), lr, st)
+        self._weights_changed()
+        return loss
 
 
 def _packed_f32(x, device):
@@ -1589,14 +1709,18 @@ class WideDeep(KerasModule):
     and gathers the wide weights (rs_wide_onehot_fwd).  The wide weight w is
     built on first use from the input width 2 nd + sum(widths).  With
     output_dim == 1 the deep tower and the head are one rs_mlp_fwd launch;
-    otherwise the reference's broadcast [B,1] + [B,output_dim] applies."""
+    otherwise the reference's broadcast [B,1] + [B,output_dim] applies.
+    ``train_step(X, labels)`` / ``train_step_onehot(dense, ids, field_offsets,
+    field_widths, labels)`` are one step of compile_fit (model/wideDeep.py:47)
+    on either form; ``w_reg`` is WideLayer's l2 factor on w."""
 
-    def __init__(self, feature_columns, hidden_units, output_dim, activation, embed_dim=8, device=None, seed=None):
+    def __init__(self, feature_columns, hidden_units, output_dim, activation, embed_dim=8, device=None, seed=None,
+                 w_reg=1e-4):
         super().__init__(device, seed)
         self.dense_feature_columns, self.sparse_feature_columns = feature_columns
         self.nd = len(self.dense_feature_columns)
         self.embed_layer = EmbedLayer(self.sparse_feature_columns, embed_dim, device=device, seed=_subseed(self._gen))
-        self.wide = WideLayer(device=device, seed=_subseed(self._gen))
+        self.wide = WideLayer(device=device, seed=_subseed(self._gen), w_reg=w_reg)
         self.deep = DNNLayer(hidden_units, output_dim, activation, device=device, seed=_subseed(self._gen))
         self.deep.build(self.embed_layer.n_fields * self.embed_layer.k)
         self.output_dim = int(output_dim)
@@ -1644,5 +1768,112 @@ class WideDeep(KerasModule):
         wide = self.wide.forward_onehot(dense if self.nd else None, ids, field_offsets, field_widths, check_ids)
         return self._combine(wide, ids, check_ids)
 
-    def train_step(self, *args, **kwargs):
-        raise NotImplementedError("WideDeep.train_step: training WideDeep is not implemented (forward only)")
+    def _train(self, wide, wide_update, ids, labels, lr, return_loss, check_ids, dropout):
+        """The step both input forms share: the deep tower forward with saved
+        activations on the embedding rows, rs_head_grad on z = 0.5 wide + 0.5
+        deep, the tower backward, then ``wide_update(g_wide)`` -> the wide
+        part's [(w, grad, n, l2)] entries (and its own launches), one
+        rs_sgd_update_multi and the row-sparse rs_embedding_sgd."""
+        deep, e = self.deep, self.embed_layer
+        layers = deep._layers()
+        rate = _dropout_rate(deep, dropout)
+        B, st, dev = ids.shape[0], _lib.stream(), self._dev
+        emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        emb = e.gather(ids, check_ids=check_ids)  # [B, F*k]: the deep input has no dense block
+        acts, drop = _dnn_train_forward(self, deep, emb, rate, st)
+        deep_out = deep.output_layer(acts[-1])
+        g_w, g_d = emp(B), emp(B)
+        loss = emp(B) if return_loss else None
+        call("rs_head_grad", ptr(wide), ptr(deep_out), ptr(labels), B, 0.5, 0.5, ptr(g_w), ptr(g_d), ptr(loss), st)
+        n = self.wide.w.shape[0]
+        gws = _gemm_ws(self, max([_lib.lib().rs_gemm_workspace_size(L.kernel.shape[0], L.kernel.shape[1], B)
+                                  for L in layers] + [_lib.lib().rs_gemm_workspace_size(n, 1, B)]))
+        gw = (ptr(gws), gws.numel())
+        grads, demb = _dnn_backward(layers, acts, g_d.view(B, 1), gw, emp, st, drop=drop)
+        dw0 = emp(1)
+        call("rs_col_sum", ptr(g_w), 1, B, 1, ptr(dw0), st)
+        # updates (every gradient above and in wide_update comes from the pre-step weights)
+        _lib.sgd_update_multi(_dnn_updates(grads) + wide_update(g_w, gw, emp, st) + [(self.wide.w0, dw0, 1, 0.0)],
+                              lr, st)
+        Fk = e.n_fields * e.k
+        ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * e.n_fields)
+        ws = self.__dict__.get("_emb_ws")
+        if ws is None or ws.numel() < ws_n:
+            ws = self.__dict__["_emb_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+        call("rs_embedding_sgd", ptr(e.table), e.total_rows, e.k, ptr(ids), _lib.id_kind(ids), ids.stride(0),
+             ptr(e.field_offsets), ptr(e.field_vocab), e.n_fields, B, ptr(demb), Fk, float(lr), ptr(ws), None, st)
+        self._weights_changed()
+        return loss
+
+    def _check_train(self, what):
+        if self._dev.type != "cuda":
+            raise NotImplementedError(f"WideDeep.{what}: training runs only on a HIP device")
+        if self.output_dim != 1:
+            raise NotImplementedError(f"WideDeep.{what}: output_dim 1 only")
+        _check_train_tower("WideDeep", self.deep)
+
+    def train_step(self, X, labels, lr=0.01, return_loss=False, check_ids=True, dropout=None):
+        """One step of compile_fit (utils/compile_fit.py:9-15; model/wideDeep.py:47)
+        on the packed row [dense | codes | dense | dummies]: BCE on sigmoid(0.5
+        (wide + deep)), WideLayer's l2(w_reg) on every element of w, plain SGD,
+        DNNLayer's Dropout active as in DeepFM.train_step.  The wide part: dw =
+        wide_in^T g (rs_gemm), dw0 = sum g (rs_col_sum), the l2 term through
+        rs_sgd_update_multi's per-tensor l2.  output_dim 1 and 'relu' / linear
+        towers only.  Returns the per-sample losses before the step if
+        ``return_loss``."""
+        self._check_train("train_step")
+        Xd = _packed_f32(X, self._dev)
+        nd, F = self.nd, self.embed_layer.n_fields
+        if Xd.dim() != 2 or Xd.shape[1] <= nd + F:
+            raise ValueError(f"WideDeep: packed input needs more than {nd + F} columns "
+                             "([dense | codes | dense | dummies])")
+        labels = _to_device_f32(labels, self._dev).reshape(-1)
+        wide_in = torch.cat([Xd[:, :nd], Xd[:, nd + F:]], dim=1)
+        B, n = wide_in.shape
+        wide = self.wide(wide_in)
+
+        def wide_update(g, gw, emp, st):
+            dw = emp(n, 1)
+            call("rs_gemm", 1, 0, n, 1, B, 1.0, ptr(wide_in), n, ptr(g), 1, 0.0, ptr(dw), 1, None, 0, *gw, st)
+            return [(self.wide.w, dw, n, self.wide.w_reg)]
+
+        return self._train(wide, wide_update, Xd[:, nd:nd + F], labels, lr, return_loss, check_ids,
+                           dropout)
+
+    def train_step_onehot(self, dense, ids, field_offsets, field_widths, labels, lr=0.01, return_loss=False,
+                          check_ids=True, dropout=None):
+        """``train_step`` on the compact form (forward_onehot's arguments): no
+        one-hot matrix is formed.  The l2 term is rs_l2_decay over all of w
+        (from the pre-step weights), the two dense halves of w each get
+        dense^T g, and the one-hot rows go through rs_embedding_sgd_strided
+        with k = 1 (each looked-up scalar of w gets its sample's g, duplicates
+        summed in lookup order)."""
+        self._check_train("train_step_onehot")
+        dev, nd = self._dev, self.nd
+        ids = _ids_tensor(ids, dev)
+        dense = _to_device_f32(dense, dev) if nd else None
+        labels = _to_device_f32(labels, dev).reshape(-1)
+        offs = torch.as_tensor(field_offsets, dtype=torch.int64).to(dev)
+        wid = torch.as_tensor(field_widths, dtype=torch.int64).to(dev)
+        B, F = ids.shape
+        wide = self.wide.forward_onehot(dense, ids, offs, wid, check_ids)
+        w = self.wide.w
+        n = w.shape[0]
+
+        def wide_update(g, gw, emp, st):
+            ups = []
+            if nd:
+                dwd = emp(nd, 1)
+                call("rs_gemm", 1, 0, nd, 1, B, 1.0, ptr(dense), dense.stride(0), ptr(g), 1, 0.0, ptr(dwd), 1, None, 0,
+                     *gw, st)
+                ups = [(ptr(w), dwd, nd, 0.0), (ptr(w) + 4 * nd, dwd, nd, 0.0)]
+            call("rs_l2_decay", ptr(w), n, float(lr), float(self.wide.w_reg), st)
+            ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * F)
+            ws = self.__dict__.get("_wide_ws")
+            if ws is None or ws.numel() < ws_n:
+                ws = self.__dict__["_wide_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+            call("rs_embedding_sgd_strided", ptr(w) + 4 * 2 * nd, n - 2 * nd, 1, ptr(ids), _lib.id_kind(ids),
+                 ids.stride(0), ptr(offs), ptr(wid), F, B, ptr(g), 1, 0, float(lr), ptr(ws), None, st)
+            return ups
+
+        return self._train(wide, wide_update, ids, labels, lr, return_loss, check_ids, dropout)
