@@ -1410,7 +1410,11 @@ int rs_shard_fm_pipe_peer(const int32_t* recv, int32_t* send,
  * rs_embed_fm_fwd_hm on that batch alone (same kernel body and tiles).
  * Shapes of the kernarg-metadata kernel only: k in {4, 8, 16}, kfm <= 15,
  * 1..32 fields (host metadata), nd <= 64, int32 / int64 ids, batch <= 8192;
- * min_blocks = 1 or 2 resident workgroups per CU (RS_ERR_ARG otherwise).    */
+ * min_blocks = 1 or 2 (RS_ERR_ARG otherwise).  Both values run the same
+ * kernel: the value was once the second __launch_bounds__ argument, which is
+ * a minimum of waves per EU, not of workgroups per CU, and a 1,024-thread
+ * workgroup already places 4 waves on every SIMD, so the two builds were
+ * identical code.  Timing one against the other measures run-to-run noise. */
 int rs_embed_fm_fwd_hm_stream(const void* ids, int id_kind, int64_t id_stride,
                               int64_t ids_batch_stride, const float* dense,
                               int64_t dense_stride, int64_t dense_batch_stride,

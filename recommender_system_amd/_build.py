@@ -30,7 +30,9 @@ ARCH = "gfx950"
 # first parameter is a struct is unaffected.  The file's other kernels that
 # start with scalars (fm_prepare_mfma, fm_prepare_generic, the diagnostic
 # probes) keep the flag's effect: it changes only how their first arguments
-# arrive, and they run once per weight set, off the hot path.
+# arrive, and they run once per weight set, off the hot path.  The other
+# kernel families around embed_fm_body (shard_fm.hip, deepfm.hip) and
+# embed_gather.hip need no entry: each of their kernels starts with a struct.
 SOURCE_FLAGS = {
     "embed_fm.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"],
 }

@@ -1,7 +1,9 @@
 // embed_fm.hpp — shared declarations of the fused gather + FM kernels
-// (embed_fm.hip: MFMA K-split kernel, sharded owner / pipe parts, DeepFM;
-// embed_fm_tiles.hip: the pipelined MFMA and VALU/DPP kernels of
-// rs_embed_fm_fwd).  Reference: FMLayer.call, layer/interaction.py:106-114.
+// (embed_fm.hip: MFMA K-split kernel; shard_fm.hip: sharded owner / pipe
+// parts; deepfm.hip: fused DeepFM; embed_gather.hip: plain gather and one-hot
+// FM; embed_fm_tiles.hip: the pipelined MFMA and VALU/DPP kernels of
+// rs_embed_fm_fwd) and the host helpers that fill their launch arguments.
+// Reference: FMLayer.call, layer/interaction.py:106-114.
 #pragma once
 #include "rs_common.hpp"
 
@@ -74,6 +76,58 @@ struct FieldMeta {
   int64_t off[32];
   int64_t voc[32];
 };
+
+// ----------------------------------------------------------- host helpers
+// The entry points' arguments as an EmbedFmArgs (everything else zero; the
+// packed image's geometry: set_geom).
+static inline EmbedFmArgs fm_args(const void* ids, int64_t id_stride, const float* dense, int64_t dense_stride, int nd,
+                                  const float* table, const int64_t* offs, const int64_t* vocab, int F, int k,
+                                  const float* prep, const float* w0, int kfm, float* logit, float* x_out,
+                                  int64_t batch, int* err) {
+  EmbedFmArgs a{};
+  a.ids = ids;
+  a.id_stride = id_stride;
+  a.dense = dense;
+  a.dense_stride = dense_stride;
+  a.nd = nd;
+  a.table = table;
+  a.offs = offs;
+  a.vocab = vocab;
+  a.F = F;
+  a.k = k;
+  a.prep = prep;
+  a.w0 = w0;
+  a.kfm = kfm;
+  a.logit = logit;
+  a.x_out = x_out;
+  a.batch = batch;
+  a.err = err;
+  return a;
+}
+
+static inline void set_geom(EmbedFmArgs& a, const FmGeom& g) {
+  a.DB = g.DB;
+  a.dense_rec = g.dense_rec;
+  a.field_rec = g.field_rec;
+  a.field_base = g.field_base;
+}
+
+// the first n (<= 32) fields' host-side (offset, vocab) pairs by value
+static inline FieldMeta field_meta(const int64_t* host_offs, const int64_t* host_vocab, int n) {
+  FieldMeta m{};
+  for (int c = 0; c < n; ++c) {
+    m.off[c] = host_offs[c];
+    m.voc[c] = host_vocab[c];
+  }
+  return m;
+}
+
+static inline int grid_for(int64_t work, int block, int cap = 2048) {
+  int64_t g = (work + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (int)g;
+}
 
 // Launches of embed_fm_tiles.hip (rs_embed_fm_fwd, id kinds 0..2): returns
 // false when the shape / option has no kernel there (the caller then runs the

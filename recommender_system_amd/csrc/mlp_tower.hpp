@@ -1,5 +1,5 @@
 // mlp_tower.hpp — device side of the fused MLP tower (mlp.hip), shared with
-// the fused DeepFM kernel (embed_fm.hip).  See mlp.hip for the design.
+// the fused DeepFM kernels (deepfm.hip, embed_fm_body.hpp).  See mlp.hip for the design.
 #pragma once
 #include <algorithm>
 #include <type_traits>

@@ -1,7 +1,7 @@
 // peer.hpp — the peer-mapped exchange's device part, shared by the standalone
 // exchange (peer.hip: rs_peer_a2a / rs_peer_gather_a2a) and the two-deep
 // pipelined sharded FM step that runs the exchange of batch t+1 inside batch
-// t's pipe launch (embed_fm.hip: rs_shard_fm_pipe_peer).  The protocol and
+// t's pipe launch (shard_fm.hip: rs_shard_fm_pipe_peer).  The protocol and
 // the mailbox layout are described at the top of peer.hip.
 #pragma once
 #include "rs_common.hpp"

@@ -79,6 +79,19 @@ inline void with_id_kind(int kind, Fn&& f) {
   }
 }
 
+// Host helper: call f(std::integral_constant<int, KV>) for a runtime row-chunk
+// width (floats per lane and field: 1, 2, 4 or 8; anything else runs as 16).
+template <class Fn>
+inline void with_kv(int KV, Fn&& f) {
+  switch (KV) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 8: f(std::integral_constant<int, 8>()); break;
+    default: f(std::integral_constant<int, 16>()); break;
+  }
+}
+
 // Device error flag: RS_FLAG_BAD_ID (an id outside [0, vocab)) unless another
 // code is given; codes are or-ed, so one flag carries every kind seen.
 __device__ __forceinline__ void flag_error(int* err_flag, int code = RS_FLAG_BAD_ID) {

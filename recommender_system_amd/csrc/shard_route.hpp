@@ -1,6 +1,6 @@
 // shard_route.hpp — field route of the sharded FM's partial protocol, shared
 // by the standalone kernel (shard.hip, rs_shard_field_route) and the fused
-// pipelined step (embed_fm.hip, rs_shard_fm_pipe).
+// pipelined step (shard_fm.hip, rs_shard_fm_pipe).
 //
 // A block split of the concatenated table (global row of (b,c) =
 // field_offsets[c] + id) gives owner o a contiguous FIELD range

@@ -1,4 +1,4 @@
-// tile_gather.hpp — the headline kernel's front end (embed_fm.hip, kernarg
+// tile_gather.hpp — the headline kernel's front end (embed_fm_body.hpp, kernarg
 // path) for the kernels that assemble a 16-sample tile of embedding rows in
 // LDS before their interaction phase: embed_cross / dcn_fused (cross.hip,
 // CrossLayer / DCN, layer/interaction.py:75-83, model/dcn.py:24-27) and

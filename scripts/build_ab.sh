@@ -7,6 +7,11 @@
 # The working tree's embed_fm.hip gets the product's per-source flags
 # (recommender_system_amd/_build.py SOURCE_FLAGS: the kernarg preload); A, an
 # older source, gets only what $AFLAGS gives it.
+# embed_fm.hip holds the FM kernel family alone (embed_fm_body.hpp: the body,
+# from the working tree for every variant); beside it the libraries link what
+# its entry points call: embed_fm_tiles.hip and capi.cpp.  (An A from before
+# the kernel families were split out of embed_fm.hip does not compile against
+# these headers: check out that commit and build its own A/B there.)
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p scripts/ab
@@ -19,7 +24,7 @@ PRELOAD="-mllvm -amdgpu-kernarg-preload-count=14"
 T=$(mktemp -d)
 variant() {  # name, embed_fm source, flags
   hipcc $F $3 -x hip -c "$2" -o $T/embed_fm_$1.o &&
-    hipcc $F ${3//$PRELOAD/} -shared $T/embed_fm_$1.o $C/embed_fm_tiles.hip $C/mlp.hip $C/capi.cpp -o scripts/ab/librs_ab_$1.so
+    hipcc $F ${3//$PRELOAD/} -shared $T/embed_fm_$1.o $C/embed_fm_tiles.hip $C/capi.cpp -o scripts/ab/librs_ab_$1.so
 }
 variant A "$A" "${AFLAGS:-}" &
 variant B $C/embed_fm.hip "$PRELOAD ${BFLAGS:-}" &
