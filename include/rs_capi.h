@@ -258,7 +258,9 @@ int rs_fm_onehot_fwd(const void* ids, int id_kind, int64_t id_stride,
  *   x_{l+1} = x0 * (x_l^T w_l) + b_l + x_l,  l = 0..L-1,  out = x_L
  * w, b: [L, d] (Keras shapes (d,1) each, stacked).  The L contractions
  * x0^T w_l run on fp32 MFMA; `prepared` (rs_cross_prepared_size floats) holds
- * the packed weights and the sample-independent bias terms.                  */
+ * the packed weights and the sample-independent bias terms.  rs_cross_fwd:
+ * L <= 32, d <= 2304, and d <= 2295 with more than 16 layers (the 16-sample
+ * tile and the waves' partial products share 160 KB of LDS).                 */
 int64_t rs_cross_prepared_size(int d, int n_layers);
 int rs_cross_prepare(const float* w, const float* b, int d, int n_layers,
                      float* prepared, rs_stream_t stream);
@@ -324,7 +326,12 @@ int rs_dcn_fwd_hm(const void* ids, int id_kind, int64_t id_stride,
 /* ----------------------------------------------- PNN inner product (a11)
  * InnerProductLayer.call (layer/interaction.py:170-183) on e[B,F,k]:
  *   out[b,p] = <e[b,i_p,:], e[b,j_p,:]>, pairs (i<j) in row-major order.
- * out row stride is out_stride (>= F(F-1)/2).                               */
+ * out row stride is out_stride (>= F(F-1)/2).  k <= 64.  n_fields <= 513
+ * (with rs_embed_inner_fwd and rs_embed_inner_fwd_hm): outside the MFMA path
+ * (k in {4,8,16,32,64}, 2..128 fields, 2..64 from ids) one thread of 256 owns
+ * the Gram rows g and F-2-g, g < F/2, so F/2 <= 256; a sample's F*k floats
+ * must also fit in 150 KB of LDS.  A larger shape returns RS_ERR_ARG and
+ * launches nothing.                                                         */
 int rs_inner_product_fwd(const float* emb, int n_fields, int k, float* out,
                          int64_t out_stride, int64_t batch, rs_stream_t stream);
 

@@ -726,6 +726,9 @@ extern "C" int rs_cross_fwd(const float* x0, int64_t x_stride, int d, int n_laye
               g_cross_dbg};
   constexpr int NW = 8;
   const size_t lds = (size_t)(((16 * d + 3) / 4) * 4 + NW * 16 * (g.NT * 16 + 1) + 16) * sizeof(float);
+  // 16 x d tile + the waves' partial G tiles: with more than 16 layers (two
+  // column tiles) the partials are 16,896 B and d = 2304 would need 164,416 B
+  RS_REQUIRE(lds <= 160 * 1024, "rs_cross_fwd: d > 2295 with more than 16 layers not supported (LDS tile)");
   const unsigned grid = (unsigned)((batch + 15) / 16);
   hipStream_t st = as_stream(stream);
   if (g.NT == 1) {

@@ -147,6 +147,7 @@ constexpr int IP_SMAX = 16;
 constexpr int IP_NW = 16, IP_NT = IP_NW * 64;  // 16 waves: one sample per wave in the Gram phase
 constexpr int IP_FMAX = 64;       // ids path: the static id tile lid[IP_SMAX][IP_FMAX]
 constexpr int IP_FMAX_EMB = 128;  // embeddings given (no id tile): bounded by the per-sample LDS tile
+constexpr int IP_FMAX_GENERIC = 513;  // inner_kernel: Gram rows g and F-2-g per thread, g < F/2 <= 256 threads
 
 // KA (inner_fast_ka, rs_embed_inner_fwd_hm / rs_embed_product_fwd_hm: K = 16,
 // <= 32 fields, 16 samples per workgroup): the rows come in through the
@@ -491,6 +492,10 @@ static int launch_inner(InnerArgs a, hipStream_t st, const char* what, const Fie
     }
     return launch_status(what);
   }
+  // inner_kernel: thread (s, g) of 256 owns Gram rows g and F-2-g, g < NG =
+  // F/2, so the F-1 rows are covered only while NG <= 256: F <= 513.
+  RS_REQUIRE(a.F <= IP_FMAX_GENERIC, "%s: n_fields <= %d (one thread per pair of Gram rows, 256 threads)", what,
+             IP_FMAX_GENERIC);
   a.NG = a.F / 2 > 0 ? a.F / 2 : 1;
   int S = 256 / a.NG;
   const int64_t per = (int64_t)a.F * a.k * sizeof(float);
@@ -499,10 +504,20 @@ static int launch_inner(InnerArgs a, hipStream_t st, const char* what, const Fie
   a.S = S;
   const size_t lds = (size_t)S * per;
   const unsigned grid = (unsigned)((a.batch + S - 1) / S);
-  if (a.k <= 8) inner_kernel<8><<<grid, 256, lds, st>>>(a);
-  else if (a.k <= 16) inner_kernel<16><<<grid, 256, lds, st>>>(a);
-  else if (a.k <= 32) inner_kernel<32><<<grid, 256, lds, st>>>(a);
-  else inner_kernel<64><<<grid, 256, lds, st>>>(a);
+  static LdsAttr set[4];
+  if (a.k <= 8) {
+    lds_attr(set[0], (const void*)inner_kernel<8>, lds);
+    inner_kernel<8><<<grid, 256, lds, st>>>(a);
+  } else if (a.k <= 16) {
+    lds_attr(set[1], (const void*)inner_kernel<16>, lds);
+    inner_kernel<16><<<grid, 256, lds, st>>>(a);
+  } else if (a.k <= 32) {
+    lds_attr(set[2], (const void*)inner_kernel<32>, lds);
+    inner_kernel<32><<<grid, 256, lds, st>>>(a);
+  } else {
+    lds_attr(set[3], (const void*)inner_kernel<64>, lds);
+    inner_kernel<64><<<grid, 256, lds, st>>>(a);
+  }
   return launch_status(what);
 }
 

@@ -133,8 +133,9 @@ __global__ __launch_bounds__(256) void pair_pool_kernel(PoolArgs a) {
   if constexpr (FM > 0) {
     pooled = a.F >= 2 ? mx : V::zero();
   } else {
-    pooled = 0.5f * (s * s - q);
-    if (a.mode == 1) pooled = a.F >= 2 ? pooled * (1.0f / (0.5f * (float)a.F * (float)(a.F - 1))) : V::zero();
+    // one field has no pair: exactly 0 (s * s - q contracts to fma(s, s, -q), the rounding residual of q)
+    pooled = a.F >= 2 ? 0.5f * (s * s - q) : V::zero();
+    if (a.mode == 1 && a.F >= 2) pooled = pooled * (1.0f / (0.5f * (float)a.F * (float)(a.F - 1)));
   }
   if (valid && a.out) {
     float* o = a.out + b * a.out_stride;
@@ -224,8 +225,8 @@ __global__ __launch_bounds__(NWP * 64) void pair_pool_ksplit(PoolArgs a) {
     s += sp[ww][lane];
     q += qp[ww][lane];
   }
-  floatx4 pooled = 0.5f * (s * s - q);
-  if (a.mode == 1) pooled = a.F >= 2 ? pooled * (1.0f / (0.5f * (float)a.F * (float)(a.F - 1))) : floatx4{0.f, 0.f, 0.f, 0.f};
+  floatx4 pooled = a.F >= 2 ? 0.5f * (s * s - q) : floatx4{0.f, 0.f, 0.f, 0.f};  // one field: no pair, exactly 0
+  if (a.mode == 1 && a.F >= 2) pooled = pooled * (1.0f / (0.5f * (float)a.F * (float)(a.F - 1)));
   if (valid && a.out) {
     float* o = a.out + b * a.out_stride;
     if (lane_ok) {

@@ -1,0 +1,1039 @@
+"""The forward interaction kernels, one entry point at a time through the C
+ABI, against plain numpy float64 restatements of the formulas in
+include/rs_capi.h, at every shape where a launcher takes another branch.
+
+Part A (CPU): every restatement is pinned to the oracle's function for the
+same operation at one small shape (1e-12), and the argument checks that refuse
+a shape before any device work are called with dummy pointers.
+
+Part B (GPU): one test per entry point, parametrised over the branch shapes
+(the mapping shape -> branch is in each test's docstring).  Row strides are
+wider than the row (NaN in the input padding, a sentinel in the output
+padding), outputs are prefilled with NaN, every optional pointer appears
+present and absent, every call runs twice on fresh outputs for bitwise
+equality, ids come as int32 / int64 / float32, and every id-driven case runs
+clean (error flag 0) and with one out-of-range id (flag raised, zero row).
+
+Inputs keep the reference O(1): embedding rows N(0,1) * 0.5 (pair pooling:
+/ sqrt(F), so the pooled sum of F^2/2 products stays O(1)), Dense kernels
+N(0,1) / sqrt(fan_in), FFM's v scaled so the interaction term is O(1),
+CrossNet's w drawn N(0,1) * 0.05 / sqrt(d) (|alpha_L| < 10 asserted on the
+reference).
+
+Tolerances: the project's contract, no new number.  Element-wise outputs
+and sums over at most a row: helpers.assert_scaled_close at 1e-5; post-sigmoid
+heads: helpers.assert_rel_close at 1e-5; products and maxima of products:
+bitwise against fp32.  Two outputs cancel past the contract, the FFM logit and
+the sum / mean pair pooling 0.5 ((sum e)^2 - sum e^2): they are bounded by
+SUM_TOL * sum |terms|, with the rounding argument in their tests' docstrings.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import ctr_oracle as O
+from recommender_system_amd import _lib
+from tests.helpers import RTOL, assert_rel_close, assert_scaled_close
+from tests.test_train_blocks import F32, F64, SENT, SUM_TOL, _d, _dev, _get, _nrm, _out, _p, _refused, _rows, _twice
+
+torch = pytest.importorskip("torch")
+
+ACTS = ("linear", "relu", "prelu", "sigmoid")  # RS_ACT_NONE .. RS_ACT_SIGMOID = 0 .. 3
+MASKED = -2.0 ** 32  # the reference's -2**32 + 1 rounds to -2**32 in fp32
+
+
+# --------------------------------------------------------------------------
+# References (float64)
+# --------------------------------------------------------------------------
+def _act(z, act, alpha=None):
+    if act == "relu":
+        return np.maximum(z, 0.0)
+    if act == "prelu":
+        return np.maximum(z, 0.0) + alpha * np.minimum(z, 0.0)
+    if act == "sigmoid":
+        return 1.0 / (1.0 + np.exp(-z))
+    return z
+
+
+def ref_dense(x, W, bias, act, alpha=None, period=1):
+    """rs_dense_fwd / rs_dense_prelu_rows_fwd: row m uses alpha row m % period."""
+    z = _d(x) @ _d(W)
+    if bias is not None:
+        z = z + _d(bias)
+    if act == "prelu":
+        alpha = _d(alpha).reshape(period, z.shape[1])[np.arange(z.shape[0]) % period]
+    return _act(z, act, alpha)
+
+
+def ref_affine_act(x, scale, shift, act, alpha=None):
+    v = _d(x)
+    if scale is not None:
+        v = v * _d(scale)
+    if shift is not None:
+        v = v + _d(shift)
+    return _act(v, act, None if alpha is None else _d(alpha))
+
+
+def ref_dice(x, mean, var, eps, alpha):
+    x = _d(x)
+    p = 1.0 / (1.0 + np.exp(-(x - _d(mean)) / np.sqrt(_d(var) + eps)))
+    return _d(alpha) * (1.0 - p) * x + p * x
+
+
+def ref_sigmoid_combine(a, b, c0, c1):
+    z = c0 * _d(a)
+    if b is not None:
+        z = z + c1 * _d(b)
+    return 1.0 / (1.0 + np.exp(-z))
+
+
+def ref_cross(x0, W, b):
+    """rs_cross_fwd: x_L, and the alpha_L of x_L = alpha_L x0 + sum_l b_l."""
+    x0, W, b = _d(x0), _d(W), _d(b)
+    x, alpha, beta = x0, np.ones(x0.shape[0]), np.zeros(x0.shape[1])
+    for l in range(W.shape[0]):
+        alpha = alpha * (1.0 + x0 @ W[l]) + beta @ W[l]
+        beta = beta + b[l]
+        x = x0 * (x @ W[l])[:, None] + b[l] + x
+    return x, alpha
+
+
+def _pairs(F):
+    return np.triu_indices(F, 1)  # row-major i < j: O.pair_indices (pinned below)
+
+
+def ref_inner(e):
+    e = _d(e)
+    i, j = _pairs(e.shape[1])
+    return np.einsum("bik,bjk->bij", e, e)[:, i, j]
+
+
+def ref_outer(e, W):
+    """out[b,p] = sum_{a,j} e[b,row_p,j] W[a,p,j] e[b,col_p,a]."""
+    e, W = _d(e), _d(W)
+    i, j = _pairs(e.shape[1])
+    return np.einsum("bpj,apj,bpa->bp", e[:, i], W, e[:, j])
+
+
+def ref_pair_products(e):
+    e = _d(e)
+    i, j = _pairs(e.shape[1])
+    return e[:, i] * e[:, j]
+
+
+def ref_pair_pool(e, mode, ab=False):
+    """rs_embed_pair_pool_fwd's pooled [B,k]: 0 sum, 1 mean, 2 max over the pairs.  ab (sum, mean): the sum
+    |terms| of 0.5 ((sum e)^2 - sum e^2) as the kernel forms it, 0.5 ((sum |e|)^2 + sum e^2)."""
+    e = _d(e)
+    B, F, k = e.shape
+    if F < 2:
+        return np.zeros((B, k))
+    if mode == 2:
+        return ref_pair_products(e).max(1)
+    s = 0.5 * (np.abs(e).sum(1) ** 2 + (e ** 2).sum(1)) if ab else 0.5 * (e.sum(1) ** 2 - (e ** 2).sum(1))
+    return s / (F * (F - 1) / 2) if mode == 1 else s
+
+
+def ref_head(pooled, w, b, n_sigmoid):
+    y = _d(pooled) @ _d(w).reshape(-1) + (0.0 if b is None else float(np.asarray(b).reshape(-1)[0]))
+    for _ in range(n_sigmoid):
+        y = 1.0 / (1.0 + np.exp(-y))
+    return y
+
+
+def _gather(table, ids, vocab):
+    """Rows of the concatenated table, [B, F, ...]; an out-of-range id reads a zero row."""
+    table, ids, vocab = np.asarray(table), np.asarray(ids, np.int64), np.asarray(vocab, np.int64)
+    offs = np.concatenate([[0], np.cumsum(vocab)[:-1]]).astype(np.int64)
+    ok = (ids >= 0) & (ids < vocab[None, :])
+    return table[np.where(ok, offs[None, :] + ids, 0)] * ok.reshape(ok.shape + (1,) * (table.ndim - 1))
+
+
+def ref_ffm(dense, ids, vocab, w0, w, v, n_sigmoid, ab=False):
+    """rs_ffm_fwd: v [feature_num, NF, k]; feature nd + offset_c + id.  ab: the sum |terms| of the logit as the
+    kernel forms it, |w0| + sum |x w| + 0.5 (sum_d (sum_f |field|)^2 + sum field^2), fields of absolute values."""
+    mag = np.abs if ab else (lambda t: t)
+    dense, w, v = mag(_d(dense)), mag(_d(w).reshape(-1)), mag(_d(v))
+    nd = dense.shape[1]
+    field = np.einsum("bi,ifk->bfk", dense, v[:nd])
+    lin = mag(float(np.asarray(w0).reshape(-1)[0])) + dense @ w[:nd]
+    if len(vocab):
+        field = field + _gather(v[nd:], ids, vocab).sum(1)
+        lin = lin + _gather(w[nd:, None], ids, vocab).sum((1, 2))
+    if ab:
+        return lin + 0.5 * ((field.sum(1) ** 2).sum(1) + (field ** 2).sum((1, 2)))
+    NF = field.shape[1]
+    y = lin + sum((field[:, f] * field[:, g]).sum(1) for f in range(NF) for g in range(f + 1, NF))
+    for _ in range(n_sigmoid):
+        y = 1.0 / (1.0 + np.exp(-y))
+    return y
+
+
+def ref_att_pool(score, mask, values):
+    """Masked softmax over t and the weighted sum of the VALUES: (out, weights)."""
+    s = np.where(np.asarray(mask) == 0, MASKED, _d(score))
+    e = np.exp(s - s.max(1, keepdims=True))
+    a = e / e.sum(1, keepdims=True)
+    return np.einsum("bt,btk->bk", a, _d(values)), a
+
+
+def _att_input(q, keys):
+    q, keys = _d(q), _d(keys)
+    qb = np.broadcast_to(q[:, None, :], keys.shape)
+    return np.concatenate([qb, keys, qb - keys, qb * keys], -1)
+
+
+def ref_att_prelu(q, keys, values, mask, layers, wo, bo):
+    """rs_din_attention_fwd (two layers) / rs_din_attention_gen_fwd (any depth):
+    layers = [(W, b, alpha [T, h])]."""
+    h = _att_input(q, keys)
+    for W, b, alpha in layers:
+        h = _act(h @ _d(W) + _d(b), "prelu", _d(alpha)[None])
+    return ref_att_pool(h @ _d(wo).reshape(-1) + float(np.asarray(bo).reshape(-1)[0]), mask, values)
+
+
+def ref_att_dice(q, keys, values, mask, dice, eps, wo, bo):
+    """rs_din_attention_dice_fwd: dice = [(alpha, mean, var)] of width 4k."""
+    h = _att_input(q, keys)
+    for alpha, mean, var in dice:
+        h = ref_dice(h, mean, var, eps, alpha)
+    return ref_att_pool(h @ _d(wo).reshape(-1) + float(np.asarray(bo).reshape(-1)[0]), mask, values)
+
+
+# --------------------------------------------------------------------------
+# A. CPU: every reference above is the oracle's function at one small shape
+# --------------------------------------------------------------------------
+def _pin(got, ref, what):
+    got, ref = _d(got), _d(ref)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert np.all(np.abs(got - ref) <= 1e-12 * np.maximum(1.0, np.abs(ref))), \
+        f"{what}: off the oracle by {float(np.max(np.abs(got - ref))):.3e}"
+
+
+def test_refs_pinned_dense_and_elementwise():
+    rng = np.random.default_rng(1)
+    M, K, N, T = 6, 5, 4, 3
+    x, W, bias = rng.normal(size=(M, K)), rng.normal(size=(K, N)), rng.normal(size=N)
+    alpha = rng.normal(size=N)
+    for act in ACTS:
+        _pin(ref_dense(x, W, bias, act, alpha), O.dense(x, W, bias, act, alpha), "dense " + act)
+    _pin(ref_dense(x, W, None, "relu"), O.dense(x, W, np.zeros(N), "relu"), "dense without bias")
+    # PReLU rows with period T: Keras Dense(N, PReLU()) on [B, T, K], alpha [T, N]
+    at = rng.normal(size=(T, N))
+    _pin(ref_dense(x, W, bias, "prelu", at, T), O.dense(x.reshape(M // T, T, K), W, bias, "prelu", at).reshape(M, N),
+         "dense prelu rows")
+    mean, var, gamma, beta = rng.normal(size=N), rng.random(N) + 0.5, rng.normal(size=N), rng.normal(size=N)
+    z, eps = rng.normal(size=(M, N)), 1e-3
+    scale = gamma / np.sqrt(var + eps)
+    for act in ACTS:
+        _pin(ref_affine_act(z, scale, beta - mean * scale, act, alpha),
+             O.activation(O.batchnorm_inference(z, mean, var, gamma, beta, eps), act, alpha), "affine " + act)
+    _pin(ref_affine_act(z, None, None, "relu"), O.activation(z, "relu"), "affine without scale and shift")
+    _pin(ref_dice(z, mean, var, eps, alpha), O.dice(z, alpha, mean, var, eps), "dice")
+    a, b = rng.normal(size=M), rng.normal(size=M)
+    _pin(ref_sigmoid_combine(a, b, 0.5, 0.25), O.sigmoid(0.5 * a + 0.25 * b), "sigmoid combine")
+    _pin(ref_sigmoid_combine(a, None, 2.0, 9.0), O.sigmoid(2.0 * a), "sigmoid combine without b")
+
+
+def test_refs_pinned_cross_and_products():
+    rng = np.random.default_rng(2)
+    B, d, L, F, k = 3, 5, 4, 5, 3
+    x0, W, b = rng.normal(size=(B, d)), rng.normal(size=(L, d)) / np.sqrt(d), rng.normal(size=(L, d))
+    x, alpha = ref_cross(x0, W, b)
+    _pin(x, O.cross_layer(x0, list(W), list(b)), "cross")
+    _pin(x, alpha[:, None] * x0 + b.sum(0), "cross: x_L = alpha_L x0 + beta_L")
+    _pin(ref_cross(x0, W[:0], b[:0])[0], x0, "cross with no layer")
+    i, j = _pairs(F)
+    ri, rj = O.pair_indices(F)
+    assert np.array_equal(i, ri) and np.array_equal(j, rj)
+    e, Wo = rng.normal(size=(B, F, k)), rng.normal(size=(k, F * (F - 1) // 2, k))
+    _pin(ref_inner(e), O.inner_product_layer(e), "inner product")
+    _pin(ref_outer(e, Wo), O.outer_product_layer(e, Wo), "outer product")
+    _pin(ref_pair_products(e), O.interaction_layer(e), "pair products")
+    _pin(ref_pair_pool(e, 0), O.bi_interaction(e), "pair pool sum")
+
+
+def test_refs_pinned_pair_pool_and_ffm():
+    rng = np.random.default_rng(3)
+    B, k, vocab = 5, 3, np.array([4, 3, 5, 2])
+    F, P = len(vocab), 6
+    tables = [rng.normal(size=(v, k)) for v in vocab]
+    ids = np.stack([rng.integers(0, v, B) for v in vocab], 1)
+    p = {"tables": tables, "out_kernel": rng.normal(size=(k, 1)), "out_bias": rng.normal(size=1),
+         "att_w_kernel": rng.normal(size=(k, P)), "att_w_bias": rng.normal(size=P),
+         "att_h_kernel": rng.normal(size=(P, 1)), "att_h_bias": rng.normal(size=1)}
+    e = _gather(np.concatenate(tables), ids, vocab)
+    for mode, name in ((0, "att"), (1, "avg"), (2, "max")):
+        out, pooled = O.afm(None, p, name, inputs=(None, ids))
+        _pin(ref_pair_pool(e, mode), pooled, "pair pool " + name)
+        _pin(ref_head(pooled, p["out_kernel"], p["out_bias"], 2), out[:, 0], "pair pool head " + name)
+    assert np.all(ref_pair_pool(e[:, :1], 1) == 0) and np.all(ref_pair_pool(e[:, :1], 2) == 0)  # no pair
+    # FFM with one out-of-range id: tf.one_hot's zero row
+    nd, kf = 2, 2
+    fn, NF = nd + int(vocab.sum()), nd + F
+    dense, w0, w, v = rng.random((B, nd)), rng.normal(size=1), rng.normal(size=(fn, 1)), rng.normal(size=(fn, NF, kf))
+    ids[1, 2], ids[3, 0] = vocab[2], -1
+    _pin(ref_ffm(dense, ids, vocab, w0, w, v, 0), O.ffm_layer(dense, ids, vocab, w0, w, v)[:, 0], "ffm logit")
+    _pin(ref_ffm(dense, ids, vocab, w0, w, v, 1), O.ffm(None, {"w0": w0, "w": w, "v": v}, vocab,
+                                                        inputs=(dense, ids))[:, 0], "ffm")
+    _pin(ref_ffm(dense, ids[:, :0], vocab[:0], w0, w[:nd], v[:nd, :nd], 0),
+         O.ffm_layer(dense, ids[:, :0], [], w0, w[:nd], v[:nd, :nd])[:, 0], "ffm without sparse fields")
+
+
+def test_refs_pinned_attention():
+    rng = np.random.default_rng(4)
+    B, T, k, eps = 4, 6, 3, 1e-3
+    q, keys, values = rng.normal(size=(B, k)), rng.normal(size=(B, T, k)), rng.normal(size=(B, T, k))
+    mask = (rng.random((B, T)) < 0.6).astype(F64)
+    mask[0], mask[1], mask[2, 1] = 0.0, 1.0, 0.5  # all masked; none masked; 0.5 is not 0: live
+    wo, bo = rng.normal(size=(5, 1)), rng.normal(size=1)
+    layers = [(rng.normal(size=(4 * k, 7)), rng.normal(size=7), rng.normal(size=(T, 7))),
+              (rng.normal(size=(7, 5)), rng.normal(size=5), rng.normal(size=(T, 5)))]
+    out, a = ref_att_prelu(q, keys, values, mask, layers, wo, bo)
+    _pin(out, O.attention(q, keys, values, mask, {"prelu": layers, "out": (wo, bo)}), "attention prelu")
+    _pin(a[0], np.full(T, 1.0 / T), "all-masked row attends uniformly")
+    wd = rng.normal(size=(4 * k, 1))
+    _pin(ref_att_prelu(q, keys, values, mask, [], wd, bo)[0],
+         O.attention(q, keys, values, mask, {"prelu": [], "out": (wd, bo)}), "attention without hidden layers")
+    dice = [(rng.normal(size=4 * k), rng.normal(size=4 * k), rng.random(4 * k) + 0.5) for _ in range(2)]
+    _pin(ref_att_dice(q, keys, values, mask, dice, eps, wd, bo)[0],
+         O.attention(q, keys, values, mask, {"dice": [(al, m, v, eps) for al, m, v in dice], "out": (wd, bo)}, "dice"),
+         "attention dice")
+
+
+# --------------------------------------------------------------------------
+# A. CPU: the inputs of the deepest CrossNet case keep the reference O(1)
+# --------------------------------------------------------------------------
+def _cross_case(d, L, B):
+    rng = np.random.default_rng(100000 + 40 * d + L)
+    x0 = _nrm(rng, B, d)
+    W, b = _nrm(rng, L, d) * F32(0.05 / np.sqrt(d)), _nrm(rng, L, d) * F32(0.1)
+    return x0, W, b
+
+
+# every d once, every L once, d = 2304 at the deepest stack that fits, every B once
+CROSS_CASES = [(1, 1, 1), (3, 16, 15), (4, 17, 16), (63, 0, 17), (65, 32, 33), (429, 16, 33), (2304, 16, 17),
+               (2295, 32, 17)]
+
+
+def test_cross_cases_stay_bounded():
+    for d, L, B in CROSS_CASES:
+        assert np.abs(ref_cross(*_cross_case(d, L, B))[1]).max() < 10.0, (d, L)
+
+
+# --------------------------------------------------------------------------
+# A. CPU: shapes past a limit are refused before any device work.  (Read for
+# each entry: the RS_REQUIRE named here precedes its first HIP call.)
+# --------------------------------------------------------------------------
+def test_forward_limits_refused_without_device():
+    lib = _lib.lib()
+    P = lambda F: F * (F - 1) // 2
+    # the generic inner-product kernel: one thread of 256 per pair of Gram rows -> n_fields <= 513;
+    # at the parent commit n_fields = 514 divided by zero on the host
+    _refused(lib.rs_inner_product_fwd(_p(1), 4, 65, _p(2), 6, 4, None), b"rs_inner_product_fwd", b"k<=64")
+    for F in (514, 515, 1026, 100000):
+        _refused(lib.rs_inner_product_fwd(_p(1), F, 1, _p(2), P(F), 4, None), b"rs_inner_product_fwd",
+                 b"n_fields <= 513")
+        _refused(lib.rs_embed_inner_fwd(_p(1), 0, F, _p(2), _p(3), _p(4), F, 1, _p(5), F + P(F), 4, None, None),
+                 b"rs_embed_inner_fwd", b"n_fields <= 513")
+        _refused(lib.rs_embed_inner_fwd_hm(_p(1), 0, F, _p(2), _p(3), _p(4), _p(5), _p(6), F, 1, _p(7), F + P(F), 4,
+                                           None, None), b"rs_embed_inner_fwd_hm", b"n_fields <= 513")
+    att = lambda T, k, H1, H2: lib.rs_din_attention_fwd(_p(1), _p(2), _p(3), _p(4), T, k, _p(5), _p(6), _p(7), H1,
+                                                         _p(8), _p(9), _p(10), H2, _p(11), _p(12), _p(13), 4, None)
+    _refused(att(8, 12, 80, 40), b"rs_din_attention_fwd", b"k must be 4, 8, 16 or 32")
+    _refused(att(8, 8, 129, 40), b"rs_din_attention_fwd", b"hidden sizes must be <= 128")
+    _refused(att(1025, 8, 80, 40), b"rs_din_attention_fwd", b"T <= 1024")
+    _refused(lib.rs_din_attention_dice_fwd(_p(1), _p(2), _p(3), _p(4), 8, 65, 0, None, None, None, 1e-3, _p(5), _p(6),
+                                           _p(7), 4, None), b"rs_din_attention_dice_fwd", b"bad shape")
+    ffm = lambda nd, F, k: lib.rs_ffm_fwd(_p(1), 0, F, _p(2), nd, nd, _p(3), _p(4), _p(5), _p(6), _p(7), F, k, 0,
+                                          _p(8), 4, None, None)
+    _refused(ffm(13, 26, 3), b"rs_ffm_fwd", b"k must divide 64")
+    # E = (nd + F) k: 1025 = 41 * 25 has no k dividing 64 but 1, which the field limits cap at 128;
+    # the smallest E past the limit that reaches the E check is 65 * 16
+    _refused(ffm(15, 26, 25), b"rs_ffm_fwd", b"k must divide 64")
+    _refused(ffm(1, 64, 16), b"rs_ffm_fwd", b"must be <= 1024")
+    _refused(ffm(0, 17, 64), b"rs_ffm_fwd", b"must be <= 1024")
+    _refused(ffm(65, 1, 1), b"rs_ffm_fwd", b"at most 64 dense")
+    pool = lambda F, k, mode, out, head_out: lib.rs_embed_pair_pool_fwd(
+        _p(1), 0, F, _p(2), _p(3), _p(4), F, k, mode, None, 0, 0, out, k, 0, _p(5), None, 0, head_out, 4, None, None)
+    _refused(pool(33, 8, 2, _p(6), None), b"rs_embed_pair_pool_fwd", b"at most 32 fields")
+    _refused(pool(4, 65, 0, _p(6), None), b"rs_embed_pair_pool_fwd", b"k <= 64")
+    _refused(pool(4, 8, 0, None, None), b"rs_embed_pair_pool_fwd", b"no output requested")
+    cross = lambda d, L, xs, ys: lib.rs_cross_fwd(_p(1), xs, d, L, _p(2), _p(3), ys, 4, None)
+    _refused(cross(2305, 2, 2305, 2305), b"rs_cross_fwd", b"d > 2304")
+    _refused(cross(8, 33, 8, 8), b"rs_cross_fwd", b"bad shape")
+    _refused(cross(8, 2, 7, 8), b"rs_cross_fwd", b"stride < d")
+    _refused(cross(8, 2, 8, 7), b"rs_cross_fwd", b"stride < d")
+    # 16 x d tile + two column tiles of partials: 164,416 B at d = 2304, past the 160 KB of LDS
+    _refused(cross(2304, 32, 2304, 2304), b"rs_cross_fwd", b"d > 2295 with more than 16 layers")
+    _refused(cross(2296, 17, 2296, 2296), b"rs_cross_fwd", b"d > 2295 with more than 16 layers")
+    dense = lambda xs, K, act, alpha: lib.rs_dense_fwd(_p(1), xs, _p(2), None, alpha, act, _p(3), 8, 4, K, 8, None)
+    _refused(dense(4, 5, 0, None), b"rs_dense_fwd", b"bad shape")
+    _refused(dense(5, 5, 2, None), b"rs_dense_fwd", b"PReLU needs alpha")
+
+
+def test_outer_prepared_size_table():
+    size = _lib.lib().rs_outer_prepared_size
+    for F in (2, 9, 39, 128):
+        for k in (4, 8, 16, 32, 64):
+            KB = (k + 15) // 16
+            assert size(F, k) == F * (F - 1) // 2 * KB * KB * 256, (F, k)
+    for F, k in ((1, 4), (0, 4), (129, 4), (26, 5), (26, 12), (26, 0), (26, 128), (-1, 16)):
+        assert size(F, k) == -1, (F, k)
+
+
+def test_attention_gen_workspace_size_formula():
+    size = _lib.lib().rs_din_attention_gen_workspace_size
+    al = lambda floats: (floats * 4 + 255) // 256 * 256
+    for B, T, k, hidden in ((1, 1, 3, ()), (4, 17, 8, (5,)), (5, 17, 65, (70, 5, 1)), (300, 100, 16, (80, 40))):
+        rows, h = B * T, max((1,) + tuple(hidden))
+        hid = (C.c_int * max(len(hidden), 1))(*hidden)
+        assert size(B, T, k, len(hidden), hid) == al(rows * 4 * k) + 2 * al(rows * h) + al(rows), (B, T, k, hidden)
+    assert size(4, 0, 8, 0, None) == -1 and size(4, 8, 0, 0, None) == -1 and size(-1, 8, 8, 0, None) == -1
+    assert size(4, 8, 8, 1, (C.c_int * 1)(0)) == -1 and size(4, 8, 8, 1, None) == -1
+
+
+# --------------------------------------------------------------------------
+# B. GPU
+# --------------------------------------------------------------------------
+WORST = {}  # kernel -> worst scaled error
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst():
+    yield
+    for k in sorted(WORST):
+        print(f"\nworst {k}: scaled {WORST[k]:.3e}", end="")
+
+
+def _record(kernel, got, ref):
+    if ref.size and np.any(ref != 0):  # an all-zero reference has no scale
+        scale = np.maximum(np.abs(ref), float(np.sqrt(np.mean(ref ** 2)))) + 1e-300
+        WORST[kernel] = max(WORST.get(kernel, 0.0), float(np.nanmax(np.abs(got - ref) / scale)))
+
+
+def _close(kernel, got, ref, what):
+    """The contract (assert_scaled_close at 1e-5), recording the worst scaled error."""
+    got, ref = np.asarray(_get(got) if hasattr(got, "detach") else got, F64).reshape(np.shape(ref)), _d(ref)
+    _record(kernel, got, ref)
+    assert_scaled_close(got, ref, RTOL, f"{kernel} {what}")
+
+
+def _rel(kernel, got, ref, what):
+    """Post-sigmoid outputs: assert_rel_close at 1e-5."""
+    got, ref = np.asarray(_get(got) if hasattr(got, "detach") else got, F64).reshape(np.shape(ref)), _d(ref)
+    if ref.size:
+        key = kernel + " (post-sigmoid, relative)"
+        WORST[key] = max(WORST.get(key, 0.0), float(np.nanmax(np.abs(got - ref) / np.abs(ref))))
+    assert_rel_close(got, ref, RTOL, f"{kernel} {what}")
+
+
+def _sum_close(kernel, got, ref, absum, what):
+    """|got - ref| <= SUM_TOL * sum |terms|: for an output that cancels (see test_ffm_fwd)."""
+    got, ref = np.asarray(_get(got) if hasattr(got, "detach") else got, F64).reshape(np.shape(ref)), _d(ref)
+    absum = _d(absum).reshape(ref.shape)
+    err, key = np.abs(got - ref), kernel + " (error / sum |terms|)"
+    ratio = np.where(absum > 0, err / np.where(absum > 0, absum, 1.0), np.where(err > 0, np.inf, 0.0))  # no term: exact
+    WORST[key] = max(WORST.get(key, 0.0), float(ratio.max()) if ratio.size else 0.0)
+    bad = ~(ratio <= SUM_TOL)
+    assert not bad.any(), f"{kernel} {what}: {int(bad.sum())}/{bad.size} outside {SUM_TOL:g} * sum|terms|; worst " \
+                          f"{float(ratio.max()):.3e}"
+
+
+KINDS = ((np.int32, _lib.ID_I32), (np.int64, _lib.ID_I64), (np.float32, _lib.ID_F32))
+
+
+def _id_case(rng, B, vocab, bad):
+    """Label codes [B, F]; bad: one out of range (the field's vocabulary size, or -1)."""
+    ids = np.stack([rng.integers(0, v, B) for v in vocab], 1).astype(np.int64) if len(vocab) else \
+        np.zeros((B, 0), np.int64)
+    if bad:
+        b, c = B // 2, len(vocab) // 2
+        ids[b, c] = vocab[c] if (B + len(vocab) + int(vocab[c])) % 2 else -1
+    return ids
+
+
+def _ids_dev(ids, dtype):
+    """Row stride F + 2; float ids carry a fraction (Keras truncates them)."""
+    a = np.asarray(ids, np.float64)
+    if dtype is np.float32:
+        a = a + 0.25 * (a >= 0)
+    return _rows(a, 2, np.nan if dtype is np.float32 else 7, dtype)
+
+
+def _meta(vocab):
+    vocab = np.asarray(vocab, np.int64)
+    return _dev(np.concatenate([[0], np.cumsum(vocab)[:-1]]), np.int64), _dev(vocab, np.int64)
+
+
+def _shifted(a, shift):
+    """The array on the device `shift` floats past a 256-B aligned address: (keep-alive, pointer)."""
+    a = np.ascontiguousarray(a, F32).reshape(-1)
+    buf = torch.full((a.size + 8,), float("nan"), dtype=torch.float32, device="cuda")
+    buf[shift:shift + a.size] = torch.from_numpy(a)
+    return buf, buf.data_ptr() + 4 * shift
+
+
+def _flag():
+    return torch.zeros(1, dtype=torch.int32, device="cuda")
+
+
+def _p_or_none(t):
+    return None if t is None else t.data_ptr()
+
+
+# ------------------------------------------------------------------ dense
+def _dense_check(name, x, W, bias, alpha, act, M, K, N, xpad, ypad, period=None, what=""):
+    st = _lib.stream()
+    xd, Wd = _rows(x, xpad), _dev(W)
+    bd, ad = (None if bias is None else _dev(bias)), (None if alpha is None else _dev(alpha))
+
+    def run():
+        y = _out(M, N, ypad)
+        if period is None:
+            _lib.call("rs_dense_fwd", xd.data_ptr(), K + xpad, Wd.data_ptr(), _p_or_none(bd), _p_or_none(ad), act,
+                      y.data_ptr(), N + ypad, M, K, N, st)
+        else:
+            _lib.call("rs_dense_prelu_rows_fwd", xd.data_ptr(), K + xpad, Wd.data_ptr(), _p_or_none(bd),
+                      ad.data_ptr(), period, y.data_ptr(), N + ypad, M, K, N, st)
+        return (y,)
+
+    ref = ref_dense(x, W, bias, ACTS[act], alpha if ACTS[act] == "prelu" else None, period or 1)
+    _close(name, _get(_twice(run)[0], N), ref, f"M={M} K={K} N={N} act={ACTS[act]} {what}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 15, 16, 17, 33])
+def test_dense_fwd(gpu, K):
+    """dense_mfma's 64 x 64 tile: M, N = 63 / 64 / 65 (a partial tile, a full one, one row or column into the next),
+    129 / 130 (three tiles), 1; its 16-deep K stage: K = 1, 15 / 16 / 17 (partial, full, one into the second), 33
+    (one into the third: both LDS buffers reused).  N = 1, 4: dense_small_n; N = 5: the first N of dense_mfma.  Every
+    (M, N) runs all four activations; bias and (for the others than PReLU) alpha are absent in turn."""
+    rng = np.random.default_rng(K)
+    for mi, M in enumerate((1, 63, 64, 65, 129)):
+        x = _nrm(rng, M, K)
+        for ni, N in enumerate((1, 4, 5, 63, 64, 65, 130)):
+            W, bias, alpha = _nrm(rng, K, N) / F32(np.sqrt(K)), _nrm(rng, N), _nrm(rng, N) * F32(0.5)
+            for act in range(4):
+                has_bias = (mi + ni + act) % 3 != 0
+                has_alpha = ACTS[act] == "prelu" or (mi + ni + act) % 2 == 0
+                _dense_check("rs_dense_fwd", x, W, bias if has_bias else None, alpha if has_alpha else None, act, M, K,
+                             N, 3, 2 * ((mi + ni) % 2), what=f"bias={has_bias}")
+
+
+@pytest.mark.gpu
+def test_dense_small_n_grid_stride(gpu):
+    """M = 16,500 rows on dense_small_n's 4,096 workgroups of 4 waves: the last 116 rows are a wave's second."""
+    rng = np.random.default_rng(16500)
+    M, K, N = 16500, 3, 1
+    x, W, bias, alpha = _nrm(rng, M, K), _nrm(rng, K, N), _nrm(rng, N), _nrm(rng, N)
+    for act in range(4):
+        _dense_check("rs_dense_fwd", x, W, bias, alpha if act == 2 else None, act, M, K, N, 1, 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [4, 5, 65])
+@pytest.mark.parametrize("alpha_rows", [1, 7, 64, 100])
+def test_dense_prelu_rows_fwd(gpu, alpha_rows, N):
+    """alpha [alpha_rows, N], row m % alpha_rows: 1 (the per-column form), 7 and 100 (no divisor of the 64-row tile:
+    the alpha row wraps inside a tile), 64 (the tile); N = 4: dense_small_n, 5 / 65: dense_mfma, one / two column
+    tiles.  z < 0 on about half the outputs, so a wrong alpha row shows."""
+    rng = np.random.default_rng(1000 * alpha_rows + N)
+    M = 3 * alpha_rows
+    for K, has_bias in ((9, True), (17, False)):
+        x, W, bias = _nrm(rng, M, K), _nrm(rng, K, N) / F32(np.sqrt(K)), _nrm(rng, N)
+        alpha = _nrm(rng, alpha_rows, N)
+        _dense_check("rs_dense_prelu_rows_fwd", x, W, bias if has_bias else None, alpha, 2, M, K, N, 3, 2,
+                     period=alpha_rows)
+
+
+# ------------------------------------------------------------ element-wise
+EW_SHAPES = [(1, 1, 0), (33, 7, 3), (8200, 257, 1)]  # the last: more than 8192 * 256 elements (the grid cap)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,pad", EW_SHAPES)
+def test_affine_act(gpu, M, N, pad):
+    """y = act(x * scale + shift): scale / shift / alpha absent in turn, all four activations; (8200, 257): the
+    8192-workgroup cap, every thread takes a second element."""
+    st = _lib.stream()
+    rng = np.random.default_rng(M + N)
+    x, scale, shift, alpha = _nrm(rng, M, N), _nrm(rng, N), _nrm(rng, N), _nrm(rng, N)
+    xd, sd, hd, ad = _rows(x, pad), _dev(scale), _dev(shift), _dev(alpha)
+    combos = [(a, s, h) for a in range(4) for s in (True, False) for h in (True, False)]
+    if M * N > 1 << 20:
+        combos = [(0, True, True), (1, False, True), (2, True, False), (3, False, False)]
+    for act, has_scale, has_shift in combos:
+        has_alpha = act == 2 or has_scale != has_shift
+
+        def run():
+            y = _out(M, N, pad + 1)
+            _lib.call("rs_affine_act", xd.data_ptr(), N + pad, sd.data_ptr() if has_scale else None,
+                      hd.data_ptr() if has_shift else None, ad.data_ptr() if has_alpha else None, act, y.data_ptr(),
+                      N + pad + 1, M, N, st)
+            return (y,)
+
+        ref = ref_affine_act(x, scale if has_scale else None, shift if has_shift else None, ACTS[act], alpha)
+        _close("rs_affine_act", _get(_twice(run)[0], N), ref, f"act={ACTS[act]} scale={has_scale} shift={has_shift}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,pad", EW_SHAPES)
+def test_dice_fwd(gpu, M, N, pad):
+    st = _lib.stream()
+    rng = np.random.default_rng(M + 2 * N)
+    x, mean, var, alpha, eps = _nrm(rng, M, N), _nrm(rng, N), rng.random(N).astype(F32) * F32(0.01), _nrm(rng, N), 0.3
+    xd, md, vd, ad = _rows(x, pad), _dev(mean), _dev(var), _dev(alpha)  # var << eps: a dropped eps shows
+
+    def run():
+        y = _out(M, N, pad + 1)
+        _lib.call("rs_dice_fwd", xd.data_ptr(), N + pad, md.data_ptr(), vd.data_ptr(), eps, ad.data_ptr(),
+                  y.data_ptr(), N + pad + 1, M, N, st)
+        return (y,)
+
+    _close("rs_dice_fwd", _get(_twice(run)[0], N), ref_dice(x, mean, var, F64(F32(eps)), alpha), "y")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 33 * 7, 8200 * 257])
+def test_sigmoid_combine(gpu, n):
+    st = _lib.stream()
+    rng = np.random.default_rng(n)
+    a, b, c0, c1 = _nrm(rng, n), _nrm(rng, n), 0.5, 0.25
+    ad, bd = _dev(a), _dev(b)
+    for has_b in (True, False):
+        def run():
+            y = _out(1, n, 2)
+            _lib.call("rs_sigmoid_combine", ad.data_ptr(), bd.data_ptr() if has_b else None, c0, c1, y.data_ptr(), n,
+                      st)
+            return (y,)
+
+        _rel("rs_sigmoid_combine", _get(_twice(run)[0], n)[0], ref_sigmoid_combine(a, b if has_b else None, c0, c1),
+             f"b={has_b}")
+
+
+# ---------------------------------------------------------------- CrossNet
+@pytest.mark.gpu
+@pytest.mark.parametrize("d,L,B", CROSS_CASES)
+def test_cross_fwd(gpu, d, L, B):
+    """L = 0 (out = x0), 1, 16 (cross_mfma<1> full), 17 (the first of cross_mfma<2>), 32 (the limit); d = 1, 3 (a
+    partial k-step), 4, 63 / 65 (around 16 k-steps), 429 (the workload), 2304 (the limit, 156,224 B of LDS at
+    L <= 16), 2295 (the limit with two column tiles: 163,840 B); B = 1, 15 / 16 / 17 (around the 16-sample tile), 33
+    (a third, partial tile).  Rows strided in and out and, for the float4 paths, dense."""
+    st = _lib.stream()
+    x0, W, b = _cross_case(d, L, B)
+    ref, alpha = ref_cross(x0, W, b)
+    assert np.abs(alpha).max() < 10.0
+    prep = torch.full((int(_lib.lib().rs_cross_prepared_size(d, L)),), float("nan"), dtype=torch.float32, device="cuda")
+    Wd, bd = (_dev(W), _dev(b)) if L else (None, None)
+    _lib.call("rs_cross_prepare", _p_or_none(Wd), _p_or_none(bd), d, L, prep.data_ptr(), st)
+    for xpad, ypad in ((3, 2), (0, 0), (0, 1), (1, 0)):
+        xd = _rows(x0, xpad)
+
+        def run():
+            y = _out(B, d, ypad)
+            _lib.call("rs_cross_fwd", xd.data_ptr(), d + xpad, d, L, prep.data_ptr(), y.data_ptr(), d + ypad, B, st)
+            return (y,)
+
+        _close("rs_cross_fwd", _get(_twice(run)[0], d), ref, f"d={d} L={L} B={B} pads=({xpad},{ypad})")
+
+
+# ------------------------------------------------- inner / outer products
+def _inner_S(F, k, fast, pairs=None):
+    """The samples per workgroup launch_inner picks (inner.hip)."""
+    if fast:
+        per, S = (F * k + 4 + pairs) * 4, 16
+        while S > 1 and S * per > 96 * 1024:
+            S -= 1
+        return S
+    S, per = 256 // max(F // 2, 1), F * k * 4
+    while S > 1 and S * per > 48 * 1024:
+        S -= 1
+    return S
+
+
+INNER_CASES = [(2, 4, True), (26, 16, True), (128, 64, True),
+               (3, 5, False), (129, 16, False), (257, 3, False), (300, 3, False), (513, 1, False), (261, 63, False)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F,k,fast", INNER_CASES)
+def test_inner_product_fwd(gpu, F, k, fast):
+    """inner_fast (k in {4,8,16,32,64}, F <= 128): (2, 4) one pair; (26, 16) the workload (two row blocks, one
+    MFMA pass); (128, 64) eight row blocks, one sample per workgroup.  inner_kernel: (3, 5) S = 256 samples per
+    workgroup, one thread each; (129, 16) F > 128 at a fast k, S = 4; (257, 3) S = 2; (300, 3) S = 1 with idle
+    threads; (513, 1) the largest F, all 256 threads; (261, 63) 65,772 B of dynamic LDS, past the 64 KiB default
+    (one batch, one stride).  B = S - 1, S, S + 1; out_stride = P (the fast kernel's float4 block) and P + 3."""
+    st = _lib.stream()
+    rng = np.random.default_rng(100 * F + k)
+    P = F * (F - 1) // 2
+    S = _inner_S(F, k, fast, P)
+    big = (F, k) == (261, 63)
+    for B in ((2,) if big else sorted({max(S - 1, 1), S, S + 1})):
+        e = _nrm(rng, B, F, k) * F32(0.5)
+        ed, ref = _dev(e), ref_inner(e)
+        for pad in ((0,) if big else (0, 3)):
+            def run():
+                y = _out(B, P, pad)
+                _lib.call("rs_inner_product_fwd", ed.data_ptr(), F, k, y.data_ptr(), P + pad, B, st)
+                return (y,)
+
+            _close("rs_inner_product_fwd", _get(_twice(run)[0], P), ref, f"F={F} k={k} B={B} pad={pad}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F,k", [(2, 4), (9, 64), (26, 16), (39, 32)])
+def test_outer_and_product_fwd(gpu, F, k):
+    """(2, 4) one pair, KB = 1; (9, 64) KB = 4 weight blocks; (26, 16) the workload; (39, 32) three row blocks, 87 KB
+    of LDS with inner and outer.  rs_product_fwd with inner only, outer only and both; out_stride = the row (the
+    float4 block where S * row is a multiple of 4) and row + 1 (per-row stores); B = 1 and S + 1."""
+    st, lb = _lib.stream(), _lib.lib()
+    rng = np.random.default_rng(10 * F + k)
+    P = F * (F - 1) // 2
+    W = _nrm(rng, k, P, k) / F32(k)
+    Wd = _dev(W)
+    prep = torch.full((int(lb.rs_outer_prepared_size(F, k)),), float("nan"), dtype=torch.float32, device="cuda")
+    _lib.call("rs_outer_prepare", Wd.data_ptr(), F, k, prep.data_ptr(), st)
+    for B in (1, _inner_S(F, k, True, 2 * P) + 1):
+        e = _nrm(rng, B, F, k) * F32(0.5)
+        ed, inner64, outer64 = _dev(e), ref_inner(e), ref_outer(e, W)
+        for pad in (0, 1):
+            def run_o():
+                y = _out(B, P, pad)
+                _lib.call("rs_outer_product_fwd", ed.data_ptr(), F, k, prep.data_ptr(), y.data_ptr(), P + pad, B, st)
+                return (y,)
+
+            _close("rs_outer_product_fwd", _get(_twice(run_o)[0], P), outer64, f"B={B} pad={pad}")
+            for inner, outer in ((1, False), (0, True), (1, True)):
+                Wrow = F * k + (P if inner else 0) + (P if outer else 0)
+
+                def run():
+                    y = _out(B, Wrow, pad)
+                    _lib.call("rs_product_fwd", ed.data_ptr(), F, k, inner, prep.data_ptr() if outer else None,
+                              y.data_ptr(), Wrow + pad, B, st)
+                    return (y,)
+
+                got, what = _get(_twice(run)[0], Wrow), f"B={B} pad={pad} inner={inner} outer={outer}"
+                assert np.array_equal(got[:, :F * k], e.reshape(B, F * k)), "flat copy " + what
+                if inner:
+                    _close("rs_product_fwd", got[:, F * k:F * k + P], inner64, "inner " + what)
+                if outer:
+                    _close("rs_product_fwd", got[:, Wrow - P:], outer64, "outer " + what)
+
+
+# ------------------------------------- pair products and the size-1 softmax
+@pytest.mark.gpu
+@pytest.mark.parametrize("F,k,B", [(2, 1, 3), (3, 5, 7), (26, 16, 5), (2, 16, 1), (26, 1, 2), (3, 16, 4),
+                                   (26, 50, 130)])
+def test_pair_products_and_attention_pool(gpu, F, k, B):
+    """F = 2 (one pair), 3, 26; k = 1, 5, 16; (26, 50, 130): B P k = 2,112,500 > 8192 * 256, the grid cap of
+    pair_products_kernel.  The products are one fp32 multiply each: bitwise.  rs_attention_pool_fwd sums the P rows
+    of the same tensor shape in order."""
+    st = _lib.stream()
+    rng = np.random.default_rng(F * 100 + k)
+    P = F * (F - 1) // 2
+    e = _nrm(rng, B, F * k)
+    ed = _rows(e, 3)
+
+    def run():
+        y = _out(B, P * k)
+        _lib.call("rs_pair_products_fwd", ed.data_ptr(), F * k + 3, F, k, B, y.data_ptr(), st)
+        return (y,)
+
+    got = _get(_twice(run)[0])
+    e3 = e.reshape(B, F, k)
+    i, j = _pairs(F)
+    assert np.array_equal(got, (e3[:, i] * e3[:, j]).reshape(B, P * k)), "not the fp32 product"
+    _close("rs_pair_products_fwd", got, ref_pair_products(e3).reshape(B, P * k), "products")
+    x = _nrm(rng, B, P * k)
+    xd = _rows(x, 5)
+
+    def run_p():
+        y = _out(B, k)
+        _lib.call("rs_attention_pool_fwd", xd.data_ptr(), P * k + 5, P, k, B, y.data_ptr(), st)
+        return (y,)
+
+    _close("rs_attention_pool_fwd", _twice(run_p)[0], _d(x).reshape(B, P, k).sum(1), "sum over the pairs")
+
+
+# ------------------------------------------------------------ pair pooling
+def _pool_variants(k):
+    """(B, nd, out_col, out_stride, out?, head_w?, head_b?, head_out?, n_sigmoid, table shift)."""
+    r4 = lambda n: (n + 3) // 4 * 4
+    v = [(1, 0, 0, r4(k), True, False, False, False, 0, 0),          # float4 stores where k % 4 == 0
+         (65, 13, 13, 13 + k + 3, True, True, True, True, 1, 0),     # out_col not a multiple of 4: dword stores
+         (65, 13, 16, r4(16 + k) + 4, True, True, False, True, 2, 0),  # out_col, out_stride multiples of 4
+         (65, 0, 0, k + 1, True, True, True, False, 0, 0),           # head_w given, head_out absent: no head
+         (1, 0, 0, 0, False, True, True, True, 0, 0)]                # out absent, the head alone
+    if k in (8, 16, 64):
+        v.append((65, 13, 16, r4(16 + k), True, True, True, True, 1, 1))  # misaligned table: the scalar form
+    return v
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 8, 12, 16, 20, 32, 33, 48, 64])
+def test_embed_pair_pool_fwd(gpu, k):
+    """float4 forms (k % 4 == 0, aligned table): G = 1 / 2 / 4 / 8 / 16 lanes per sample at k = 4 / 8 / 16 / 32 /
+    64, idle quads at k = 12 / 20 / 48; scalar forms: G = 1 / 2 / 4 / 8 / 64 at k = 1 / 2 / 3 / 5 / 33, and G = 8 /
+    16 / 64 at k = 8 / 16 / 64 with the table one float off 16-B alignment.  Sum / mean: pair_pool_ksplit (float4)
+    takes 32 fields per pass, F = 33 / 70 need a second / third; pair_pool_kernel (scalar) chunks of 32 fields.
+    'max': the 32 fields in registers, F = 32 the limit; F = 1: no pair, exactly 0 in every mode.  'max' is also
+    bitwise the fp32 maximum of the fp32 products.  Sum and mean are 0.5 ((sum e)^2 - sum e^2), which cancels: with
+    two fields and one of them out of range (a zero row) the exact value is 0 and the kernel returns the rounding
+    residual of e^2 (k = 1: e = -1.7568355, kernel -3.2595e-09; numpy fp32 with the kernel's fma(s, s, -q) gives
+    the same -3.2595153e-09), which no bound relative to the output admits.  So sum and mean are bounded by
+    SUM_TOL * sum |terms|, sum |terms| = 0.5 ((sum |e|)^2 + sum e^2) (6.2e-06 in that case); 'max' and the heads
+    keep the contract."""
+    st = _lib.stream()
+    rng = np.random.default_rng(7000 + k)
+    variants = _pool_variants(k)
+    for mode in (0, 1, 2):
+        for fi, F in enumerate((1, 2, 26, 32) + ((33, 70) if mode != 2 else ())):
+            vocab = rng.integers(3, 12, F)
+            table = (_nrm(rng, int(vocab.sum()), k) / F32(np.sqrt(F)))
+            offd, vocd = _meta(vocab)
+            hw, hb = _nrm(rng, k) / F32(np.sqrt(k)), _nrm(rng, 1)
+            hwd, hbd = _dev(hw), _dev(hb)
+            tabs = {s: _shifted(table, s) for s in (0, 1) if s == 0 or k in (8, 16, 64)}
+            for vi, (B, nd, col, stride, want_out, has_hw, has_hb, want_head, n_sig, shift) in enumerate(variants):
+                dtype, kind = KINDS[(vi + fi + mode) % 3]
+                dense = _nrm(rng, B, nd)
+                dd = _rows(dense, 3) if nd else None
+                out0 = np.full((B, max(stride, 1)), SENT, F32)
+                out0[:, :nd] = np.nan
+                out0[:, col:col + k] = np.nan
+                for bad in (False, True):
+                    ids = _id_case(rng, B, vocab, bad)
+                    idd = _ids_dev(ids, dtype)
+
+                    def run(with_flag=True):
+                        flag = _flag()
+                        out, head = _dev(out0) if want_out else None, _out(B, 1) if want_head else None
+                        _lib.call("rs_embed_pair_pool_fwd", idd.data_ptr(), kind, F + 2, tabs[shift][1],
+                                  offd.data_ptr(), vocd.data_ptr(), F, k, mode, _p_or_none(dd), nd + 3, nd,
+                                  _p_or_none(out), stride, col, hwd.data_ptr() if has_hw else None,
+                                  hbd.data_ptr() if has_hb else None, n_sig, _p_or_none(head), B,
+                                  flag.data_ptr() if with_flag else None, st)
+                        return tuple(t for t in (flag, out, head) if t is not None)
+
+                    res = list(_twice(run))
+                    what = f"mode={mode} F={F} variant={vi} kind={kind} bad={bad}"
+                    if bad:
+                        assert all(torch.equal(x, y) for x, y in zip(res[1:], run(False)[1:])), \
+                            "err_flag = NULL changes an output " + what
+                    assert int(res.pop(0).item()) == (_lib.FLAG_BAD_ID if bad else 0), "error flag " + what
+                    e32 = _gather(table, ids, vocab).astype(F32)
+                    pooled = ref_pair_pool(e32, mode)
+                    if want_out:
+                        got = _get(res.pop(0))
+                        rest = np.ones(stride, bool)
+                        rest[:nd], rest[col:col + k] = False, False
+                        assert np.all(got[:, rest] == SENT), "wrote outside its columns " + what
+                        assert np.array_equal(got[:, :nd], dense), "dense pass-through " + what
+                        if mode == 2:
+                            _close("rs_embed_pair_pool_fwd", got[:, col:col + k], pooled, what)
+                        else:
+                            _record("rs_embed_pair_pool_fwd", got[:, col:col + k], pooled)
+                            _sum_close("rs_embed_pair_pool_fwd", got[:, col:col + k], pooled,
+                                       ref_pair_pool(e32, mode, ab=True), what)
+                        if mode == 2 and F >= 2:
+                            i, j = _pairs(F)
+                            assert np.array_equal(got[:, col:col + k], (e32[:, i] * e32[:, j]).max(1)), \
+                                "'max' is not the fp32 maximum of the fp32 products " + what
+                    if want_head:
+                        y = ref_head(pooled, hw, hb if has_hb else None, n_sig)
+                        (_rel if n_sig else _close)("rs_embed_pair_pool_fwd", _get(res.pop(0))[:, 0], y, "head " + what)
+
+
+# --------------------------------------------------------------------- FFM
+FFM_CASES = [  # (nd, n_fields, k, floats v is off 16-B alignment)
+    (13, 26, 4, 0),   # ffm4_kernel NS = 1 (39 float4 per row)
+    (13, 26, 8, 0),   # ffm4_kernel NS = 2
+    (0, 16, 64, 0),   # ffm4_kernel NS = 4, E = 1024 (the limit), no dense field
+    (0, 1, 4, 0),     # one field: no pair
+    (13, 26, 1, 0),   # ffm_kernel NS = 1
+    (13, 26, 2, 0),   # ffm_kernel NS = 2
+    (64, 64, 1, 0),   # ffm_kernel NS = 2, every lane a dense and a sparse field
+    (3, 5, 16, 1),    # misaligned v: ffm_kernel NS = 2 at k % 4 == 0
+    (3, 6, 16, 1),    # ffm_kernel NS = 4 (144 elements)
+    (13, 26, 8, 1),   # ffm_kernel NS = 8 (312 elements)
+    (0, 16, 64, 1),   # ffm_kernel NS = 16 (1024 elements)
+    (3, 0, 4, 0),     # no sparse field, float4 form
+    (3, 0, 2, 0),     # no sparse field, scalar form
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nd,F,k,shift", FFM_CASES)
+def test_ffm_fwd(gpu, nd, F, k, shift):
+    """v is scaled so that sum_d T_d^2 and sum F^2 are O(1) (the logit is half their difference, plus w0 and the
+    linear term).  The logit cancels, so with B = 1 (rms = |logit|) the contract asks for 1e-5 of a number far
+    smaller than its terms: at (13, 26, 1), B = 1 the logit is -0.0057114 = (-0.3803 + 0.4501) + 0.5 (0.6123 -
+    0.7633) and the kernel is 7.0e-8 off, 1.27e-5 scaled.  That is rounding: ffm_kernel restated in numpy fp32 in
+    the kernel's order (fields in order, the dense fmas, the xor-butterfly lane sums) gives -0.0057112873, 7.25e-8
+    off the fp64 value, the same 1.27e-5 scaled.  So the logit is bounded by SUM_TOL * sum |terms| (sum |terms|
+    from the reference on absolute values, as the batch sums of test_train_blocks.py); the worst scaled error is
+    still recorded.  The post-sigmoid output keeps the relative contract."""
+    st = _lib.stream()
+    rng = np.random.default_rng(1000 * nd + 10 * F + k + shift)
+    vocab = rng.integers(2, 7, F)
+    NF, fn = nd + F, nd + int(vocab.sum())
+    v = _nrm(rng, fn, NF, k) / F32(np.sqrt(NF * k * (nd / 3 + F)))
+    w, w0 = _nrm(rng, fn) * F32(0.1), _nrm(rng, 1)
+    vbuf, vptr = _shifted(v, shift)
+    wd, w0d = _dev(w), _dev(w0)
+    offd, vocd = _meta(vocab) if F else (None, None)
+    for B in (1, 5):
+        dense = rng.random((B, nd)).astype(F32)
+        dd = _rows(dense, 3) if nd else None
+        for n_sig in (0, 1):
+            for dtype, kind in KINDS if F else KINDS[:1]:
+                for bad in (False, True) if F else (False,):
+                    ids = _id_case(rng, B, vocab, bad)
+                    idd = _ids_dev(ids, dtype) if F else None
+
+                    def run(with_flag=True):
+                        flag, y = _flag(), _out(B, 1)
+                        _lib.call("rs_ffm_fwd", _p_or_none(idd), kind, F + 2, _p_or_none(dd), nd + 3, nd, vptr,
+                                  wd.data_ptr(), w0d.data_ptr(), _p_or_none(offd), _p_or_none(vocd), F, k, n_sig,
+                                  y.data_ptr(), B, flag.data_ptr() if with_flag else None, st)
+                        return flag, y
+
+                    flag, y = _twice(run)
+                    what = f"B={B} n_sigmoid={n_sig} kind={kind} bad={bad}"
+                    if bad:
+                        assert torch.equal(y, run(False)[1]), "err_flag = NULL changes the output " + what
+                    assert int(flag.item()) == (_lib.FLAG_BAD_ID if bad else 0), "error flag " + what
+                    ref = ref_ffm(dense, ids, vocab, w0, w, v, n_sig)
+                    if n_sig:
+                        _rel("rs_ffm_fwd", _get(y)[:, 0], ref, what)
+                    else:
+                        _sum_close("rs_ffm_fwd", _get(y)[:, 0], ref, ref_ffm(dense, ids, vocab, w0, w, v, 0, ab=True),
+                                   what)
+                        _record("rs_ffm_fwd", _get(y)[:, 0], ref)
+
+
+# --------------------------------------------------------------- attention
+def _att_case(rng, B, T, k):
+    """Distinct keys and values; a mask with holes, row 0 fully live, row 1 (B > 1) fully masked, one 0.5."""
+    q, keys, values = _nrm(rng, B, k) * F32(0.5), _nrm(rng, B, T, k) * F32(0.5), _nrm(rng, B, T, k)
+    mask = (rng.random((B, T)) < 0.7).astype(F32)
+    mask[0] = 1.0
+    if B > 1:
+        mask[1] = 0.0
+    if B > 2:
+        mask[2, T // 2] = 0.5
+    return q, keys, values, mask
+
+
+def _att_layers(rng, T, widths, n_in):
+    layers = []
+    for h in widths:
+        layers.append((_nrm(rng, n_in, h) / F32(np.sqrt(n_in)), _nrm(rng, h) * F32(0.1), _nrm(rng, T, h) * F32(0.5)))
+        n_in = h
+    return layers, _nrm(rng, n_in) / F32(np.sqrt(n_in)), _nrm(rng, 1)
+
+
+def _att_checks(kernel, out, ref, a, mask, what):
+    T = mask.shape[1]
+    live = (mask != 0).sum(1)
+    if T >= 16:
+        assert a[live >= 16].max() < 0.9, "the reference's softmax saturates: the pool would not be tested"
+    _close(kernel, out, ref, what)
+
+
+ATT_CASES = (
+    [(T, 8, 80, 40, 4) for T in (1, 16, 17, 64, 65, 1024)] +  # one tile, a full one, 1 + 1/16, 4, 4 + 1/16, the limit
+    [(17, k, 80, 40, 5) for k in (4, 16, 32)] +               # KQ = 1 / 4 / 8
+    [(17, 8, 1, 1, 1),        # H = 1: the scalar alpha reads, a single unit
+     (17, 8, 7, 3, 5),        # H % 4 != 0: a1vec / a2vec false
+     (17, 8, 80, 48, 4),      # HT = (5, 3): the <5,3> instance, full
+     (17, 8, 81, 48, 4),      # H1 = 81: HT1 = 6 -> <8,8>, H1 % 4 != 0
+     (17, 8, 80, 49, 4),      # H2 = 49: HT2 = 4 -> <8,8>, H2 % 4 != 0
+     (17, 8, 128, 128, 5),    # the largest widths
+     (17, 32, 128, 128, 4),   # 147,456 B of LDS, the largest
+     (1, 4, 4, 4, 16400)])    # more samples than the 4,096 workgroups of 4 waves take in one pass
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T,k,H1,H2,B", ATT_CASES)
+def test_din_attention_fwd(gpu, T, k, H1, H2, B):
+    st = _lib.stream()
+    rng = np.random.default_rng(T * 1000 + k * 100 + H1 + H2)
+    q, keys, values, mask = _att_case(rng, B, T, k)
+    layers, wo, bo = _att_layers(rng, T, (H1, H2), 4 * k)
+    ref, a = ref_att_prelu(q, keys, values, mask, layers, wo, bo)
+    dv = [_dev(t) for t in (q, keys, values, mask)]
+    (W1, b1, a1), (W2, b2, a2) = [[_dev(t) for t in l] for l in layers]
+    wod, bod = _dev(wo), _dev(bo)
+
+    def run():
+        out = _out(B, k)
+        _lib.call("rs_din_attention_fwd", *[t.data_ptr() for t in dv], T, k, W1.data_ptr(), b1.data_ptr(),
+                  a1.data_ptr(), H1, W2.data_ptr(), b2.data_ptr(), a2.data_ptr(), H2, wod.data_ptr(), bod.data_ptr(),
+                  out.data_ptr(), B, st)
+        return (out,)
+
+    _att_checks("rs_din_attention_fwd", _twice(run)[0], ref, a, mask, f"T={T} k={k} H=({H1},{H2}) B={B}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 5, 16, 64])
+def test_din_attention_dice_fwd(gpu, k):
+    """k = 1, 16, 64 divide 64; k = 5 leaves 4 idle lanes in the pool's (position group, dim) layout.  T = 1, 65 (a
+    second round of 64 positions); n_dice = 0 (the concat straight into Dense(1)), 1, 3.  var << eps."""
+    st = _lib.stream()
+    rng = np.random.default_rng(50 + k)
+    eps, B = 0.3, 5
+    for T in (1, 65):
+        q, keys, values, mask = _att_case(rng, B, T, k)
+        dv = [_dev(t) for t in (q, keys, values, mask)]
+        for n_dice in (0, 1, 3):
+            dice = [(_nrm(rng, 4 * k) * F32(0.5), _nrm(rng, 4 * k) * F32(0.2),
+                     rng.random(4 * k).astype(F32) * F32(0.01)) for _ in range(n_dice)]
+            wo, bo = _nrm(rng, 4 * k) / F32(np.sqrt(4 * k)), _nrm(rng, 1)
+            ref, a = ref_att_dice(q, keys, values, mask, dice, F64(F32(eps)), wo, bo)
+            stack = lambda i: _dev(np.stack([d[i] for d in dice])) if n_dice else None
+            al, mean, var, wod, bod = stack(0), stack(1), stack(2), _dev(wo), _dev(bo)
+
+            def run():
+                out = _out(B, k)
+                _lib.call("rs_din_attention_dice_fwd", *[t.data_ptr() for t in dv], T, k, n_dice, _p_or_none(al),
+                          _p_or_none(mean), _p_or_none(var), eps, wod.data_ptr(), bod.data_ptr(), out.data_ptr(), B, st)
+                return (out,)
+
+            _att_checks("rs_din_attention_dice_fwd", _twice(run)[0], ref, a, mask, f"T={T} k={k} n_dice={n_dice}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("widths", [(), (1,), (5,), (70,), (70, 5, 1)])
+@pytest.mark.parametrize("k", [3, 8, 65])
+def test_din_attention_gen_fwd(gpu, k, widths):
+    """k = 3 (no divisor of 64), 8, 65 (att_masked_pool's k > 64 branch: a lane per dim, two rounds); 0, 1 and 3
+    hidden layers of widths 1 (dense_small_n with PReLU rows), 5 (the first N of dense_mfma), 70 (two column tiles);
+    T = 1, 17.  The workspace is exactly the reported size; the bytes after it must stay untouched."""
+    st, lb = _lib.stream(), _lib.lib()
+    rng = np.random.default_rng(10 * k + sum(widths))
+    B, n = 5, len(widths)
+    for T in (1, 17):
+        q, keys, values, mask = _att_case(rng, B, T, k)
+        layers, wo, bo = _att_layers(rng, T, widths, 4 * k)
+        ref, a = ref_att_prelu(q, keys, values, mask, layers, wo, bo)
+        dv = [_dev(t) for t in (q, keys, values, mask)]
+        dl = [[_dev(t) for t in l] for l in layers]
+        wod, bod = _dev(wo), _dev(bo)
+        hid = (C.c_int * max(n, 1))(*widths)
+        pa = lambda i: (C.c_void_p * max(n, 1))(*[l[i].data_ptr() for l in dl])
+        size = int(lb.rs_din_attention_gen_workspace_size(B, T, k, n, hid))
+
+        def run():
+            out = _out(B, k)
+            ws = torch.full((size + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+            _lib.call("rs_din_attention_gen_fwd", *[t.data_ptr() for t in dv], T, k, n, hid, pa(0), pa(1), pa(2),
+                      wod.data_ptr(), bod.data_ptr(), out.data_ptr(), B, ws.data_ptr(), size, st)
+            return out, ws[size:]
+
+        out, tail = _twice(run)
+        assert bool((tail == 0xA5).all()), "wrote past the reported workspace size"
+        _att_checks("rs_din_attention_gen_fwd", out, ref, a, mask, f"T={T} k={k} widths={widths}")
