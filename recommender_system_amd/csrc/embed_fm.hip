@@ -20,8 +20,10 @@
 //   * s = x@v and the linear term x@w1 come out of v_mfma_f32_16x16x4_f32
 //     (B columns 0..kfm-1 = v, column kfm = w1); the second-order correction
 //     sum_f (x^2@v^2)_f = sum_i x_i^2 * |v_i|^2 is a per-lane FMA with the row
-//     norms packed beside B, reduced across the 4 k-slots by wave shuffles.
-//   * Partial tiles of the NW waves are summed through LDS; wave 0 finishes
+//     norms packed beside B, reduced across the 4 k-slots by two lane swaps
+//     (v_permlane16_swap / v_permlane32_swap: no LDS round trip).
+//   * Partial tiles of the NW waves are summed through LDS ([sample][column]
+//     [wave]: a thread's 16 partials in four 16-B reads); wave 0 finishes
 //     logit = (x@w1 + w0) + 0.5*(sum_f s_f^2 - sum_i x_i^2 |v_i|^2).
 #include <stdlib.h>
 

@@ -56,19 +56,31 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
   constexpr int MAXC = MAXC0 < 1 ? 1 : (MAXC0 > 8 ? 8 : MAXC0);
   typedef Ids<(KIND >= 3) ? 0 : KIND> I;
   constexpr bool OWNER = KIND == 4;
-  __shared__ float cs[NW][16][NT * 16 + 1];
+  // partial tiles of the NW waves for the combine: [sample][column][wave], a
+  // thread's NW partials contiguous (16-B reads; the row of CW floats is
+  // padded by 4 so they stay 16-B aligned); the fused tower (TW), whose LDS
+  // budget counts the old size, keeps [wave][sample][column + 1]
+  constexpr int NC = NT * 16;  // columns per sample
+  constexpr bool WIDE = !TW && NW % 4 == 0;
+  constexpr int CW = NW + 4;
+  __shared__ __attribute__((aligned(16))) float cs[WIDE ? 16 * NC * CW : NW * 16 * (NC + 1)];
   __shared__ float qs[NW][16];
 
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int s = lane & 15;   // A: sample row of the tile; B/C: column
   const int kk = lane >> 4;  // k-slot
+  // (specialised shapes: the row length is the instantiation's, not an argument to wait for)
+  const int ak = FC > 0 ? 4 * KV : a.k;
   const int64_t bt = (int64_t)tile * 16 + s;
   const bool valid = bt < a.batch;
   // Padded lanes of the last tile recompute the last sample: an MFMA output
   // row depends only on its own A row, so they never touch valid outputs.
-  const int64_t b = bt < a.batch ? bt : a.batch - 1;
-  const int d = and_ + aF * a.k;
+  // (the kernarg kernels are launched for at most 512 tiles: the sample index
+  // is an unsigned 32-bit value, so b * stride is a 32 x 64-bit multiply)
+  const int64_t b = (KA && !TW) ? (int64_t)(uint32_t)(valid ? (int)bt : (int)a.batch - 1)
+                                : (bt < a.batch ? bt : a.batch - 1);
+  const int d = and_ + aF * ak;
   // w0 is requested now, not behind the rows (a dependent load at the end;
   // PL: its pointer is a cold argument, so with those — late_args below)
   float w0v = (OWNER || PL) ? 0.f : a.w0[0];
@@ -117,7 +129,7 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
     mlp_first_fill<NW>(*tw, ring);
     float* par = tsm + 32 * tw->rs + NW * 256;
     for (int i = threadIdx.x; i < tw->ptot; i += NW * 64) par[i] = tw->prep[tw->wtot + i];
-    const int d0 = aF * a.k + and_, padw = tw->Kp[0] - d0;
+    const int d0 = aF * ak + and_, padw = tw->Kp[0] - d0;
     for (int i = threadIdx.x; i < 16 * padw; i += NW * 64) {
       const int r = i / padw;
       tsm[r * xrs + d0 + (i - r * padw)] = 0.f;
@@ -201,8 +213,12 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
 #ifdef RS_DIAG_STAMPS
         if (a.ablate & 2) { P.bw[j][nt].zero(); P.bw[j][nt].v[0] = (float)P.cj[j]; continue; }
 #endif
-        // lanes of the zero-padded columns (> kfm) load nothing
-        if (nt * 16 + s <= akfm) P.bw[j][nt].load(rec + (int64_t)(nt * 64 + lane) * KV);
+        // kernarg kernels: every lane loads — the packed image holds zeros in
+        // its padded columns (> kfm; fm_prepare_mfma writes fm_bval's 0.f
+        // there), the value the masked form puts in their place, and the exec
+        // masking is code in front of the id loads.  The kernels with several
+        // tiles per CU keep the mask (13.67 vs 13.61 us at B 16,384 without it).
+        if (KA || nt * 16 + s <= akfm) P.bw[j][nt].load(rec + (int64_t)(nt * 64 + lane) * KV);
         else P.bw[j][nt].zero();
       }
     }
@@ -223,6 +239,12 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
         P.nrm[j][tp] = row16_sum(sq);
       }
   };
+  constexpr int PS = NW * MAXC;  // fields per pass
+  // PF: B fragments of the first two passes ride the id trip (registers: two
+  // passes only where they are few; larger rows load theirs per pass).
+  // Measured (scripts/ab, profiles/r3_ab_prefetch_*.json): 14.51 vs 15.30 us
+  // at batch 16384 (4 tiles per CU), 6.15 vs 6.13 at 4096 (1 tile per CU)
+  constexpr bool PRE = PF && KV * MAXC * NT <= 8;
   const int wv = threadIdx.x >> 6;
   // a pass's ids and field metadata (issue_rows takes them from here)
   auto fetch_ids = [&](int cg, Pass& P) {
@@ -254,7 +276,8 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
         }
       }
     }
-    if (cg == 0 && !coop && aF > 0) load_dense();
+    // (the two-pass schedule below requests the dense block itself, once)
+    if (!PRE && cg == 0 && !coop && aF > 0) load_dense();
   };
   // id -> table row (the ids must have arrived)
   auto decode_rows = [&](int cg, Pass& P) {
@@ -282,7 +305,7 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
 #ifdef RS_DIAG_STAMPS
       if ((a.ablate & 8) && cg + j * NW + w >= aF) { P.xs[j].zero(); continue; }
 #endif
-      P.xs[j].load_nt(a.table + P.row[j] * a.k + KV * kk);
+      P.xs[j].load_nt(a.table + P.row[j] * ak + KV * kk);
     }
   };
   auto issue_rows = [&](int cg, Pass& P, bool fetched) {
@@ -315,12 +338,12 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
       }
       if constexpr (TW) {
         if (live) {
-          float* xo = tsm + s * xrs + P.cj[j] * a.k + KV * kk;
+          float* xo = tsm + s * xrs + P.cj[j] * ak + KV * kk;
 #pragma unroll
           for (int tp = 0; tp < KV; ++tp) xo[tp] = P.ok[j] ? P.xs[j].v[tp] : 0.f;
         }
       } else if (!KA && a.x_out && live && valid) {  // (the kernarg kernel never emits x)
-        float* xo = a.x_out + b * d + and_ + P.cj[j] * a.k + KV * kk;
+        float* xo = a.x_out + b * d + and_ + P.cj[j] * ak + KV * kk;
 #pragma unroll
         for (int tp = 0; tp < KV; ++tp) xo[tp] = P.ok[j] ? P.xs[j].v[tp] : 0.f;
       }
@@ -332,31 +355,27 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
   // one slot per wave: a wave with no field left in a pass stops there (a
   // wave-uniform exit; nothing after the loop needs its slot)
   auto has_pass = [&](int cg) { return cg < aF && !(MAXC == 1 && cg + w >= aF); };
-  constexpr int PS = NW * MAXC;  // fields per pass
-  // PF: B fragments of the first two passes ride the id trip (registers: two
-  // passes only where they are few; larger rows load theirs per pass).
-  // Measured (scripts/ab, profiles/r3_ab_prefetch_*.json): 14.51 vs 15.30 us
-  // at batch 16384 (4 tiles per CU), 6.15 vs 6.13 at 4096 (1 tile per CU)
-  constexpr bool PRE = PF && KV * MAXC * NT <= 8;
   // PL: the cold arguments' one batched s_load completes under the id trip —
   // they are first needed here, behind the B-fragment and id loads (whose
   // addresses come from preloaded SGPRs and compile-time geometry only)
   auto late_args = [&]() {
     if constexpr (PL) {
       w0v = a.w0[0];
-      asm volatile("" ::"s"(a.k), "s"(a.logit), "s"(a.w0), "s"(a.err));
+      if constexpr (FC == 0) asm volatile("" ::"s"(a.k));
+      asm volatile("" ::"s"(a.logit), "s"(a.w0), "s"(a.err));
     }
   };
   Pass P0, P1;
+  // (every wave has a first field where the field count is a constant >= NW)
+  const bool one = FC >= NW || has_pass(0), two = has_pass(PS);
   if (PRE) {
-    if (has_pass(0)) issue_b(0, P0);
-    if (has_pass(PS)) issue_b(PS, P1);
+    if (one) issue_b(0, P0);
+    if (two) issue_b(PS, P1);  // (a second field implies a first)
   }
   if (aF == 0 || coop) load_dense();
   if (coop) __syncthreads();
   RS_STAMP(9);
   if (PRE) {
-    const bool one = has_pass(0), two = one && has_pass(PS);
     if (one) {
       // both passes' ids requested together: the second pass's id trip is
       // not serialised behind the first pass's rows and MFMAs (after the B
@@ -364,27 +383,54 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
       // with the arguments preloaded, 5.94 vs 5.63)
       fetch_ids(0, P0);
       if (two) fetch_ids(PS, P1);
-    } else if (!coop && aF > 0) {
-      load_dense();  // a wave with no field (F < NW) may still own a dense k-step
     }
+    // the dense block, once, behind the ids (a wave with no field, F < NW,
+    // may still own a dense k-step)
+    if (!coop && aF > 0) load_dense();
     late_args();
     if (one) {
-      // (the second pass's rows stay behind the first pass's MFMAs: issuing
-      // them with the first pass's was slower, 6.19 vs 5.82 us at 4096 —
-      // the r1 finding that two row bursts beat one, again)
       issue_rows(0, P0, true);
       // (PL: w0, requested in late_args, is taken here, under the row trip —
       // left alone its load sinks behind the MFMAs, a dependent trip at the end)
       if constexpr (PL) asm volatile("" ::"s"(w0v));
       norms(P0);
       if (two) norms(P1);
-      // the second pass's ids arrive with the first's: its row addresses are
-      // worked out while the first rows are in flight, so only the loads
-      // themselves sit between the first pass's MFMAs and the second trip
-      if (two) decode_rows(PS, P1);
+      // the second pass's ids arrive with the first's: its row offsets are
+      // worked out while the first rows are in flight and pinned in registers
+      // (the empty asm), so only the loads themselves are left for later
+      int64_t ro[MAXC];
+#pragma unroll
+      for (int j = 0; j < MAXC; ++j) ro[j] = 0;
+      if (two) {
+        decode_rows(PS, P1);
+#pragma unroll
+        for (int j = 0; j < MAXC; ++j) {
+          ro[j] = P1.row[j] * ak + KV * kk;
+          asm volatile("" : "+v"(ro[j]));
+        }
+      }
+      // The second burst leaves the moment the first rows are here, and the
+      // first pass's MFMAs run underneath it (both bursts at once was slower,
+      // 6.19 vs 5.82 us at 4096 — the r1 finding that two row bursts beat one
+      // — and the second burst behind the first pass's MFMAs left its loads
+      // waiting for four waves' MFMAs on one matrix pipe: DESIGN 4.1).  Every
+      // wave waits for its first rows HERE, in front of the branch: a wait
+      // behind the join would be a vmcnt(0) that takes the second burst with it.
+      asm volatile("" ::"v"(P0.xs[MAXC - 1].v[KV - 1]));
+      __builtin_amdgcn_sched_barrier(0);
+      if (two) {
+#pragma unroll
+        for (int j = 0; j < MAXC; ++j) {
+#ifdef RS_DIAG_STAMPS
+          if ((a.ablate & 8) && PS + j * NW + w >= aF) { P1.xs[j].zero(); continue; }
+#endif
+          P1.xs[j].load_nt(a.table + ro[j]);
+        }
+        RS_STAMP(15);
+      }
+      __builtin_amdgcn_sched_barrier(0);
       consume(0, P0);
       if (two) {
-        load_rows(PS, P1);
         consume(PS, P1);
         // (a third pass: more than 2 x NW fields — never in the kernarg kernel, F <= 32)
         for (int cg = 2 * PS; !KA && has_pass(cg); cg += PS) {
@@ -413,7 +459,7 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
     for (int nt = 0; nt < NT; ++nt) ac[nt][0] = mfma16x16x4(dx, drec[nt], ac[nt][0]);
     qn = fmaf(dx * dx, dn, qn);
     if constexpr (TW) {
-      if (e < and_) tsm[s * xrs + aF * a.k + e] = dx;
+      if (e < and_) tsm[s * xrs + aF * ak + e] = dx;
     } else if (!KA && a.x_out && valid && e < and_) {
       a.x_out[b * d + e] = dx;
     }
@@ -428,7 +474,7 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
       for (int nt = 0; nt < NT; ++nt) ac[nt][0] = mfma16x16x4(x, rec[nt * 64 + lane], ac[nt][0]);
       qn = fmaf(x * x, rec[NT * 64 + kk], qn);
       if constexpr (TW) {
-        if (e < and_) tsm[s * xrs + aF * a.k + e] = x;
+        if (e < and_) tsm[s * xrs + aF * ak + e] = x;
       } else if (a.x_out && valid && e < and_) {
         a.x_out[b * d + e] = x;
       }
@@ -454,18 +500,37 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) cs[w][kk * 4 + r][nt * 16 + s] = acc[nt][r];
-  qn += __shfl_xor(qn, 16);
-  qn += __shfl_xor(qn, 32);
+    for (int r = 0; r < 4; ++r) {
+      const int smp = kk * 4 + r, col = nt * 16 + s;
+      cs[WIDE ? (smp * NC + col) * CW + w : (w * 16 + smp) * (NC + 1) + col] = acc[nt][r];
+    }
+  // the k-slots' q partials meet in registers: the lane swaps exchange rows
+  // 16 apart, then the wave's halves, without an LDS round trip; every lane
+  // adds the same two values as an xor-16 / xor-32 shuffle pair would (float
+  // addition commutes), so (q0 + q1) + (q2 + q3) keeps its bits
+  __builtin_amdgcn_sched_barrier(0);  // the tile writes go out first
+  const auto h = __builtin_amdgcn_permlane16_swap(__float_as_uint(qn), __float_as_uint(qn), false, false);
+  qn = __uint_as_float(h[0]) + __uint_as_float(h[1]);
+  const auto f = __builtin_amdgcn_permlane32_swap(__float_as_uint(qn), __float_as_uint(qn), false, false);
+  qn = __uint_as_float(f[0]) + __uint_as_float(f[1]);
   if (lane < 16) qs[w][lane] = qn;
   __syncthreads();
   RS_STAMP(7);
-  constexpr int NC = NT * 16;  // columns per sample
   if (threadIdx.x < 16 * NC) {
     const int smp = threadIdx.x / NC, col = threadIdx.x % NC;
+    // the waves' partials in wave order 0 .. NW-1, from 0.f
     float v = 0.f;
+    if constexpr (WIDE) {
+      const floatx4* pw = reinterpret_cast<const floatx4*>(cs + (smp * NC + col) * CW);
+      floatx4 pv[NW / 4];
 #pragma unroll
-    for (int ww = 0; ww < NW; ++ww) v += cs[ww][smp][col];
+      for (int g = 0; g < NW / 4; ++g) pv[g] = pw[g];
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) v += pv[ww / 4][ww % 4];
+    } else {
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) v += cs[(ww * 16 + smp) * (NC + 1) + col];
+    }
     float t = col < akfm ? v * v : 0.f;       // s_f^2
     if (col < NW) t -= qs[col][smp];           // - sum_i x_i^2 |v_i|^2 (wave partials)
     float lin = col == akfm ? v : 0.f;        // x@w1

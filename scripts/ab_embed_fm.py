@@ -76,8 +76,13 @@ def main():
                     fn(i)
         torch.cuda.synchronize()
         graphs[n], outs[n] = g, logit
+    # Round -1 is a warm-up, reported apart: the first timed round of a process
+    # reads high for whichever build goes first (5.70 against 5.65-5.66 us in
+    # the seven after it, 14.3 against 13.5 at B 16,384 — the clocks and the
+    # graph's first replays, not the build), which would count as that arm's spread.
     res = {n: [] for n in names}
-    for r in range(8):
+    warm = {}
+    for r in range(-1, 8):
         for n in (names if r % 2 == 0 else names[::-1]):
             g = graphs[n]
             g.replay()
@@ -88,12 +93,18 @@ def main():
                 g.replay()
             e1.record()
             torch.cuda.synchronize()
-            res[n].append(e0.elapsed_time(e1) * 1e3 / (10 * NP))
+            us = e0.elapsed_time(e1) * 1e3 / (10 * NP)
+            if r < 0:
+                warm[n] = round(us, 3)
+            else:
+                res[n].append(us)
     ref = outs["A"]
     rms = float(ref.pow(2).mean().sqrt())
     diff = {n: float(((outs[n] - ref).abs() / ref.abs().clamp_min(rms)).max()) for n in names}
     print(json.dumps({**{"us_per_launch_" + n: [round(x, 3) for x in res[n]] for n in names},
                       **{"median_" + n: round(float(np.median(res[n])), 3) for n in names},
+                      **{"spread_" + n: round(max(res[n]) - min(res[n]), 3) for n in names},
+                      "warmup_round_us": warm,
                       "max_scaled_diff_vs_A": diff, "err": int(err.item())}))
 
 

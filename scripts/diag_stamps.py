@@ -1,7 +1,8 @@
 """Phase timeline of one rs_embed_fm_fwd launch (diagnostic library with
 s_memrealtime stamps, 100 MHz, scripts/build_diag.sh): per workgroup / wave
   t0 start, t5 kernel arguments, per pass p (0: t6 row issue, t1 ids decoded,
-  t2 rows arrived, t13 MFMAs done; 1: t10, t11, t12, t14), t3 wave's MFMAs
+  t2 rows arrived, t13 MFMAs done; 1: t10, t11, t12, t14; t15 the second
+  pass's rows issued, in front of the first pass's MFMAs), t3 wave's MFMAs
   done (dense included), t7 combine barrier released, t4 end (wave 0).
 RS_DIAG_HM=1 runs the kernarg-metadata kernel (rs_embed_fm_fwd_hm's), DIAG_OPT
 sets RS_OPT_EMBED_FM_KERNEL.  Prints percentiles (us) relative to the
@@ -68,6 +69,8 @@ def main():
            "p0 mfma (t13 - t2)": pct(t[:, :, 13] - t[:, :, 2]),
            "p1 ids decoded (t11 - t0)": pct(t[:, w2, 11] - t[:, w2, 0]),
            "p1 row issue after p0 rows (t10 - t2)": pct(t[:, w2, 10] - t[:, w2, 2]),
+           "p1 rows issued to p0 mfma start (t2 - t15)": pct(t[:, w2, 2] - t[:, w2, 15]),
+           "p1 rows arrived after p0 rows (t12 - t2)": pct(t[:, w2, 12] - t[:, w2, 2]),
            "p1 rows arrived (t12 - t10)": pct(t[:, w2, 12] - t[:, w2, 10]),
            "p1 mfma (t14 - t12)": pct(t[:, w2, 14] - t[:, w2, 12]),
            "wave done (t3) 2-field waves": pct(t[:, w2, 3] - base),
