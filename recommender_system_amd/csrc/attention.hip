@@ -348,9 +348,7 @@ static unsigned att_grid(int64_t batch) {
 template <int KQ, int HT1M, int HT2M>
 static int launch_att(const AttArgs& a, hipStream_t st) {
   const size_t lds = (size_t)(a.HT1 * 4 * KQ * 64 + a.HT2 * a.HT1 * 4 * 64 + ATT_WAVES * ATT_TMAX) * sizeof(float);
-  auto fn = din_attention_mfma<KQ, HT1M, HT2M>;
-  if (lds > 65536) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  fn<<<att_grid(a.batch), ATT_WAVES * 64, lds, st>>>(a);
+  launch_lds<din_attention_mfma<KQ, HT1M, HT2M>>(att_grid(a.batch), ATT_WAVES * 64, lds, st, a);
   return launch_status("rs_din_attention_fwd");
 }
 

@@ -731,27 +731,12 @@ extern "C" int rs_cross_fwd(const float* x0, int64_t x_stride, int d, int n_laye
   RS_REQUIRE(lds <= 160 * 1024, "rs_cross_fwd: d > 2295 with more than 16 layers not supported (LDS tile)");
   const unsigned grid = (unsigned)((batch + 15) / 16);
   hipStream_t st = as_stream(stream);
-  if (g.NT == 1) {
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)cross_mfma<1, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    cross_mfma<1, NW><<<grid, NW * 64, lds, st>>>(a);
-  } else {
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)cross_mfma<2, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    cross_mfma<2, NW><<<grid, NW * 64, lds, st>>>(a);
-  }
+  if (g.NT == 1) launch_lds<cross_mfma<1, NW>>(grid, NW * 64, lds, st, a);
+  else launch_lds<cross_mfma<2, NW>>(grid, NW * 64, lds, st, a);
   return launch_status("rs_cross_fwd");
 }
 
 namespace rs {
-// host field metadata -> FieldMeta for the kernarg front end (k = 16, <= 32 fields), else null
-static const FieldMeta* host_meta(FieldMeta& m, const int64_t* off_h, const int64_t* voc_h, int n_fields, int k) {
-  if (!off_h || !voc_h || k != 16 || n_fields < 1 || n_fields > 32) return nullptr;
-  for (int c = 0; c < n_fields; ++c) {
-    m.off[c] = off_h[c];
-    m.voc[c] = voc_h[c];
-  }
-  return &m;
-}
-
 static int embed_cross_run(const void* ids, int id_kind, int64_t id_stride, const float* dense,
                            int64_t dense_stride, int nd, const float* table, const int64_t* field_offsets,
                            const int64_t* field_vocab, int n_fields, int k, int n_layers, const float* prepared,
@@ -782,27 +767,12 @@ static int embed_cross_run(const void* ids, int id_kind, int64_t id_stride, cons
   hipStream_t st = as_stream(stream);
   with_id_kind(id_kind, [&](auto K) {
     constexpr int KIND = decltype(K)::value;
-    if (hm && g.NT == 1 && opt(RS_OPT_CROSS_KERNEL) == 0) {
-      static LdsAttr setr;
-      lds_attr(setr, (const void*)embed_cross_ka<1, KIND, true>, lds);
-      embed_cross_ka<1, KIND, true><<<grid, NW * 64, lds, st>>>(a, e, *hm);
-    } else if (hm && g.NT == 1) {
-      static LdsAttr setk1;
-      lds_attr(setk1, (const void*)embed_cross_ka<1, KIND>, lds);
-      embed_cross_ka<1, KIND><<<grid, NW * 64, lds, st>>>(a, e, *hm);
-    } else if (hm) {
-      static LdsAttr setk2;
-      lds_attr(setk2, (const void*)embed_cross_ka<2, KIND>, lds);
-      embed_cross_ka<2, KIND><<<grid, NW * 64, lds, st>>>(a, e, *hm);
-    } else if (g.NT == 1) {
-      static LdsAttr set1;
-      lds_attr(set1, (const void*)embed_cross<1, KIND>, lds);
-      embed_cross<1, KIND><<<grid, NW * 64, lds, st>>>(a, e);
-    } else {
-      static LdsAttr set2;
-      lds_attr(set2, (const void*)embed_cross<2, KIND>, lds);
-      embed_cross<2, KIND><<<grid, NW * 64, lds, st>>>(a, e);
-    }
+    if (hm && g.NT == 1 && opt(RS_OPT_CROSS_KERNEL) == 0)
+      launch_lds<embed_cross_ka<1, KIND, true>>(grid, NW * 64, lds, st, a, e, *hm);
+    else if (hm && g.NT == 1) launch_lds<embed_cross_ka<1, KIND>>(grid, NW * 64, lds, st, a, e, *hm);
+    else if (hm) launch_lds<embed_cross_ka<2, KIND>>(grid, NW * 64, lds, st, a, e, *hm);
+    else if (g.NT == 1) launch_lds<embed_cross<1, KIND>>(grid, NW * 64, lds, st, a, e);
+    else launch_lds<embed_cross<2, KIND>>(grid, NW * 64, lds, st, a, e);
   });
   return launch_status("rs_embed_cross_fwd");
 }
@@ -828,7 +798,7 @@ extern "C" int rs_embed_cross_fwd_hm(const void* ids, int id_kind, int64_t id_st
   FieldMeta m;
   return embed_cross_run(ids, id_kind, id_stride, dense, dense_stride, nd, table, field_offsets, field_vocab,
                          n_fields, k, n_layers, prepared, out, out_stride, batch, err_flag, stream,
-                         host_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
+                         kernarg_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
 }
 
 namespace rs {
@@ -883,35 +853,18 @@ static int dcn_run(const void* ids, int id_kind, int64_t id_stride, const float*
     const bool reg = opt(RS_OPT_CROSS_KERNEL) == 0;
     if (hm && g.NT == 1 && mlp_tail_ok(t.Np, t.Kp, t.N, t.L, 1, gwa, gwb) && gwa == 8 && gwb == 2) {
       // the split-K tail at the reference's 256-128-64 tower
-      if (reg) {
-        static LdsAttr setktr;
-        lds_attr(setktr, (const void*)dcn_fused_ka<1, KIND, true, true>, lds);
-        dcn_fused_ka<1, KIND, true, true><<<grid, 16 * 64, lds, st>>>(a, e, t, *hm);
-      } else {
-        static LdsAttr setkt;
-        lds_attr(setkt, (const void*)dcn_fused_ka<1, KIND, true>, lds);
-        dcn_fused_ka<1, KIND, true><<<grid, 16 * 64, lds, st>>>(a, e, t, *hm);
-      }
+      if (reg) launch_lds<dcn_fused_ka<1, KIND, true, true>>(grid, 16 * 64, lds, st, a, e, t, *hm);
+      else launch_lds<dcn_fused_ka<1, KIND, true>>(grid, 16 * 64, lds, st, a, e, t, *hm);
     } else if (hm && g.NT == 1 && reg) {
-      static LdsAttr setk1r;
-      lds_attr(setk1r, (const void*)dcn_fused_ka<1, KIND, false, true>, lds);
-      dcn_fused_ka<1, KIND, false, true><<<grid, 16 * 64, lds, st>>>(a, e, t, *hm);
+      launch_lds<dcn_fused_ka<1, KIND, false, true>>(grid, 16 * 64, lds, st, a, e, t, *hm);
     } else if (hm && g.NT == 1) {
-      static LdsAttr setk1;
-      lds_attr(setk1, (const void*)dcn_fused_ka<1, KIND>, lds);
-      dcn_fused_ka<1, KIND><<<grid, 16 * 64, lds, st>>>(a, e, t, *hm);
+      launch_lds<dcn_fused_ka<1, KIND>>(grid, 16 * 64, lds, st, a, e, t, *hm);
     } else if (hm) {
-      static LdsAttr setk2;
-      lds_attr(setk2, (const void*)dcn_fused_ka<2, KIND>, lds);
-      dcn_fused_ka<2, KIND><<<grid, 16 * 64, lds, st>>>(a, e, t, *hm);
+      launch_lds<dcn_fused_ka<2, KIND>>(grid, 16 * 64, lds, st, a, e, t, *hm);
     } else if (g.NT == 1) {
-      static LdsAttr set1;
-      lds_attr(set1, (const void*)dcn_fused<1, KIND>, lds);
-      dcn_fused<1, KIND><<<grid, 16 * 64, lds, st>>>(a, e, t);
+      launch_lds<dcn_fused<1, KIND>>(grid, 16 * 64, lds, st, a, e, t);
     } else {
-      static LdsAttr set2;
-      lds_attr(set2, (const void*)dcn_fused<2, KIND>, lds);
-      dcn_fused<2, KIND><<<grid, 16 * 64, lds, st>>>(a, e, t);
+      launch_lds<dcn_fused<2, KIND>>(grid, 16 * 64, lds, st, a, e, t);
     }
   });
   return launch_status("rs_dcn_fwd");
@@ -939,7 +892,7 @@ extern "C" int rs_dcn_fwd_hm(const void* ids, int id_kind, int64_t id_stride, co
   FieldMeta m;
   return dcn_run(ids, id_kind, id_stride, dense, dense_stride, nd, table, field_offsets, field_vocab, n_fields, k,
                  n_cross, cross_prepared, n_layers, dims, acts, mlp_prepared, out, batch, err_flag, stream,
-                 host_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
+                 kernarg_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
 }
 
 // diagnostics only: per-wave phase stamps of the CrossNet kernels (null = off)

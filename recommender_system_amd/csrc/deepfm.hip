@@ -606,43 +606,24 @@ static void launch_deepfm(const EmbedFmArgs& a, const MlpArgs& t, size_t lds, hi
       int gwa = 0, gwb = 0;
       const bool tail = mlp_tail_ok(t.Np, t.Kp, t.N, t.L, 1, gwa, gwb) && gwa == 8 && gwb == 2;
       const bool ring4 = opt(RS_OPT_DEEPFM_KERNEL) == 3;
-      static LdsAttr all_set[3];
-      auto go = [&](const void* k, LdsAttr& set, auto launch) {
-        lds_attr(set, k, lds);
-        launch();
-      };
-      if (tail && ring4)
-        go((const void*)deepfm_all<KIND, 27, 4, 8, 2>, all_set[0],
-           [&] { deepfm_all<KIND, 27, 4, 8, 2><<<grid, 16 * 64, lds, st>>>(a, t, *hm); });
-      else if (tail)
-        go((const void*)deepfm_all<KIND, 27, 3, 8, 2>, all_set[1],
-           [&] { deepfm_all<KIND, 27, 3, 8, 2><<<grid, 16 * 64, lds, st>>>(a, t, *hm); });
-      else
-        go((const void*)deepfm_all<KIND, 27, 3>, all_set[2],
-           [&] { deepfm_all<KIND, 27, 3><<<grid, 16 * 64, lds, st>>>(a, t, *hm); });
+      if (tail && ring4) launch_lds<deepfm_all<KIND, 27, 4, 8, 2>>(grid, 16 * 64, lds, st, a, t, *hm);
+      else if (tail) launch_lds<deepfm_all<KIND, 27, 3, 8, 2>>(grid, 16 * 64, lds, st, a, t, *hm);
+      else launch_lds<deepfm_all<KIND, 27, 3>>(grid, 16 * 64, lds, st, a, t, *hm);
       return;
     }
     if (deepfm_ws_ok(a, t, hm, KV)) {
       // layers 1.. as the split-K tail at the DeepFM widths (256 -> 128 -> 64 -> 1), else mlp_tower_tile
       int gwa = 0, gwb = 0;
-      static LdsAttr ws_set[2];
-      if (mlp_tail_ok(t.Np, t.Kp, t.N, t.L, 1, gwa, gwb) && gwa == 8 && gwb == 2) {
-        lds_attr(ws_set[0], (const void*)deepfm_ws<KIND, 27, 8, 2>, lds);
-        deepfm_ws<KIND, 27, 8, 2><<<grid, 16 * 64, lds, st>>>(a, t, *hm);
-      } else {
-        lds_attr(ws_set[1], (const void*)deepfm_ws<KIND, 27>, lds);
-        deepfm_ws<KIND, 27><<<grid, 16 * 64, lds, st>>>(a, t, *hm);
-      }
+      if (mlp_tail_ok(t.Np, t.Kp, t.N, t.L, 1, gwa, gwb) && gwa == 8 && gwb == 2)
+        launch_lds<deepfm_ws<KIND, 27, 8, 2>>(grid, 16 * 64, lds, st, a, t, *hm);
+      else launch_lds<deepfm_ws<KIND, 27>>(grid, 16 * 64, lds, st, a, t, *hm);
       return;
     }
   }
-  static LdsAttr lds_set[2];  // opt in to exactly what is needed beyond the default
   // the kernarg body is built lean for at most 16 dense k-steps (nd <= 64):
   // its dense loop is compiled out (embed_fm_body: dense_small = KA || ...)
-  const int ka = hm && a.F <= 32 && a.DB <= 16 ? 1 : 0;
-  lds_attr(lds_set[ka], ka ? (const void*)deepfm_fused_ka<KV, KIND> : (const void*)deepfm_fused<KV, KIND>, lds);
-  if (ka) deepfm_fused_ka<KV, KIND><<<grid, 16 * 64, lds, st>>>(a, t, *hm);
-  else deepfm_fused<KV, KIND><<<grid, 16 * 64, lds, st>>>(a, t);
+  if (hm && a.F <= 32 && a.DB <= 16) launch_lds<deepfm_fused_ka<KV, KIND>>(grid, 16 * 64, lds, st, a, t, *hm);
+  else launch_lds<deepfm_fused<KV, KIND>>(grid, 16 * 64, lds, st, a, t);
 }
 
 }  // namespace rs

@@ -135,9 +135,6 @@ extern "C" int rs_diag_wave_slots(int grid, int block, int lds_bytes, uint32_t* 
     rs::set_error("rs_diag_wave_slots: bad arguments");
     return RS_ERR_ARG;
   }
-  if (lds_bytes > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)rs::diag_wave_slots_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              lds_bytes);
-  rs::diag_wave_slots_kernel<<<grid, block, lds_bytes, (hipStream_t)stream>>>(out);
+  rs::launch_lds<rs::diag_wave_slots_kernel>(grid, block, lds_bytes, (hipStream_t)stream, out);
   return rs::launch_status("rs_diag_wave_slots");
 }

@@ -895,17 +895,10 @@ static void launch_din_h(const DinArgs& a, hipStream_t st) {
   if (a.g.HT1 == 5 && a.g.HT2 == 3) {  // reference (80, 40)
     const size_t lds = df_lds(a.g);
     if (opt(RS_OPT_DIN_KERNEL) == 0 && lds) {
-      DinArgs b = a;
       const unsigned grid = (unsigned)((a.batch + DF_SPW - 1) / DF_SPW);
-      if (KS == 2 && a.g.NTT == 7) {  // config 4 (k 8, T 97..112)
-        static LdsAttr set7;
-        lds_attr(set7, (const void*)din_fused<KS, 5, 3, KIND, 7>, lds);
-        din_fused<KS, 5, 3, KIND, 7><<<grid, DF_NW * 64, lds, st>>>(b);
-        return;
-      }
-      static LdsAttr set;
-      lds_attr(set, (const void*)din_fused<KS, 5, 3, KIND>, lds);
-      din_fused<KS, 5, 3, KIND><<<grid, DF_NW * 64, lds, st>>>(b);
+      if (KS == 2 && a.g.NTT == 7)  // config 4 (k 8, T 97..112)
+        launch_lds<din_fused<KS, 5, 3, KIND, 7>>(grid, DF_NW * 64, lds, st, a);
+      else launch_lds<din_fused<KS, 5, 3, KIND>>(grid, DF_NW * 64, lds, st, a);
       return;
     }
     launch_din<KS, 5, 3, KIND, true>(a, st);
@@ -1008,15 +1001,9 @@ static bool din_tower_ok(const DinGeom& g, int n_layers, const int* dims, MlpGeo
 template <int KS, int KIND>
 static void launch_din_tower(const DinArgs& a, const DinTower& tw, size_t lds, hipStream_t st) {
   const unsigned grid = (unsigned)((a.batch + DF_SPW - 1) / DF_SPW);
-  if (KS == 2 && a.g.NTT == 7) {  // config 4 (k 8, T 97..112)
-    static LdsAttr set7;
-    lds_attr(set7, (const void*)din_fused_tower<KS, 5, 3, KIND, 7>, lds);
-    din_fused_tower<KS, 5, 3, KIND, 7><<<grid, DF_NW * 64, lds, st>>>(a, tw);
-    return;
-  }
-  static LdsAttr set;
-  lds_attr(set, (const void*)din_fused_tower<KS, 5, 3, KIND>, lds);
-  din_fused_tower<KS, 5, 3, KIND><<<grid, DF_NW * 64, lds, st>>>(a, tw);
+  if (KS == 2 && a.g.NTT == 7)  // config 4 (k 8, T 97..112)
+    launch_lds<din_fused_tower<KS, 5, 3, KIND, 7>>(grid, DF_NW * 64, lds, st, a, tw);
+  else launch_lds<din_fused_tower<KS, 5, 3, KIND>>(grid, DF_NW * 64, lds, st, a, tw);
 }
 }  // namespace rs
 

@@ -1098,14 +1098,9 @@ extern "C" int rs_din_att_prelu_fwd(const float* h0, const float* W1, const floa
   const int SA = slots((a.Rp >> 4) * (a.h1p >> 4)), SB = slots((a.Rp >> 4) * (a.h2p >> 4));
   const size_t lds = (size_t)o * sizeof(float);
   hipStream_t st = as_stream(stream);
-  auto go = [&](auto fn) {
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    fn<<<(unsigned)G, 512, lds, st>>>(a);
-  };
   if (SA <= 5 && SB <= 3 && att_bwd_nv(T, K0) <= 2)
-    go(din_att_fwd_kernel<5, 3, 2>);
-  else
-    go(din_att_fwd_kernel<8, 8, 4>);
+    launch_lds<din_att_fwd_kernel<5, 3, 2>>((unsigned)G, 512, lds, st, a);
+  else launch_lds<din_att_fwd_kernel<8, 8, 4>>((unsigned)G, 512, lds, st, a);
   return launch_status("rs_din_att_prelu_fwd");
 }
 
@@ -1148,16 +1143,11 @@ extern "C" int rs_din_att_prelu_bwd(const float* h0, const float* z1, const floa
   auto slots = [](int tiles) { return (tiles + AB_NW - 1) / AB_NW; };
   const int SA = slots((a.Rp >> 4) * (a.h1p >> 4)), SB = slots((a.h1p >> 4) * (a.h2p >> 4)),
             SC = slots((a.K0p >> 4) * (a.h1p >> 4));
-  auto go = [&](auto fn) {
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    fn<<<(unsigned)G, 512, lds, st>>>(a);
-  };
   // fewer slots / vectors = fewer live registers: the (80, 40) default at
   // T <= 112 (K0 = 32) takes the small instance; the general one spills
   if (SA <= 5 && SB <= 2 && SC <= 2 && att_bwd_nv(T, K0) <= 2 && att_bwd_nv(T, h1) <= 4 && att_bwd_nv(T, h2) <= 2)
-    go(din_att_bwd_kernel<5, 2, 2, 2, 4, 2>);
-  else
-    go(din_att_bwd_kernel<8, 8, 8, 4, 4, 4>);
+    launch_lds<din_att_bwd_kernel<5, 2, 2, 2, 4, 2>>((unsigned)G, 512, lds, st, a);
+  else launch_lds<din_att_bwd_kernel<8, 8, 8, 4, 4, 4>>((unsigned)G, 512, lds, st, a);
   const AttBwdOut o{dW1, db1, dalpha1, dW2, db2, dalpha2, dwo, dbo};
   din_att_bwd_fin<<<(unsigned)((a.P + 63) / 64), 256, 0, st>>>(a.part, G, a, o);
   return launch_status("rs_din_att_prelu_bwd");

@@ -876,9 +876,9 @@ extern "C" int rs_outer_product_bwd(const float* emb, int64_t emb_stride, const 
                  emb_stride >= n_fields * k && demb_stride >= n_fields * k &&
                  dout_stride >= n_fields * (n_fields - 1) / 2,
              "rs_outer_product_bwd: bad arguments (2 <= n_fields <= 64, 1 <= k <= 16)");
-  const size_t lds = (size_t)16 * (n_fields * k + 1) * sizeof(float);
-  outer_bwd_kernel<<<(unsigned)((batch + 15) / 16), 1024, lds, as_stream(stream)>>>(
-      emb, emb_stride, dout, dout_stride, W, n_fields, k, batch, demb, demb_stride);
+  const size_t lds = (size_t)16 * (n_fields * k + 1) * sizeof(float);  // 65,600 B at 64 fields, k = 16
+  launch_lds<outer_bwd_kernel>((unsigned)((batch + 15) / 16), 1024, lds, as_stream(stream), emb, emb_stride, dout,
+                               dout_stride, W, n_fields, k, batch, demb, demb_stride);
   return launch_status("rs_outer_product_bwd");
 }
 

@@ -122,6 +122,15 @@ static inline FieldMeta field_meta(const int64_t* host_offs, const int64_t* host
   return m;
 }
 
+// the same into m for the kernarg front ends of the cross and product
+// families (k = 16, 1..32 fields, both host arrays given), else null
+static inline const FieldMeta* kernarg_meta(FieldMeta& m, const int64_t* host_offs, const int64_t* host_vocab, int n,
+                                            int k) {
+  if (!host_offs || !host_vocab || k != 16 || n < 1 || n > 32) return nullptr;
+  m = field_meta(host_offs, host_vocab, n);
+  return &m;
+}
+
 static inline int grid_for(int64_t work, int block, int cap = 2048) {
   int64_t g = (work + block - 1) / block;
   if (g < 1) g = 1;

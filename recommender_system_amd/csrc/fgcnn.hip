@@ -256,18 +256,8 @@ static int fg_launch(const char* what, FgArgs& a, int id_kind, const int* filter
   a.S = S;
   const size_t lds = ((size_t)a.wtot + (size_t)S * a.per) * sizeof(float);
   const unsigned grid = (unsigned)((a.batch + S - 1) / S);
-  if (a.ids == nullptr) {
-    static LdsAttr set;
-    lds_attr(set, (const void*)fgcnn_conv<3>, lds);
-    fgcnn_conv<3><<<grid, FG_NT, lds, st>>>(a);
-  } else {
-    with_id_kind(id_kind, [&](auto KI) {
-      constexpr int KIND = decltype(KI)::value;
-      static LdsAttr set[3];
-      lds_attr(set[KIND], (const void*)fgcnn_conv<KIND>, lds);
-      fgcnn_conv<KIND><<<grid, FG_NT, lds, st>>>(a);
-    });
-  }
+  if (a.ids == nullptr) launch_lds<fgcnn_conv<3>>(grid, FG_NT, lds, st, a);
+  else with_id_kind(id_kind, [&](auto KI) { launch_lds<fgcnn_conv<decltype(KI)::value>>(grid, FG_NT, lds, st, a); });
   return launch_status(what);
 }
 

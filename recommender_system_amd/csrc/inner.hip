@@ -443,11 +443,11 @@ __global__ __launch_bounds__(IP_NT) void inner_fast_ka(InnerArgs a, FieldMeta m)
 template <int KIND>
 static void launch_inner_fast_k(const InnerArgs& a, size_t lds, unsigned grid, hipStream_t st) {
   switch (a.k) {
-    case 4: inner_fast<4, KIND><<<grid, IP_NT, lds, st>>>(a); break;
-    case 8: inner_fast<8, KIND><<<grid, IP_NT, lds, st>>>(a); break;
-    case 16: inner_fast<16, KIND><<<grid, IP_NT, lds, st>>>(a); break;
-    case 32: inner_fast<32, KIND><<<grid, IP_NT, lds, st>>>(a); break;
-    default: inner_fast<64, KIND><<<grid, IP_NT, lds, st>>>(a); break;
+    case 4: launch_lds<inner_fast<4, KIND>>(grid, IP_NT, lds, st, a); break;
+    case 8: launch_lds<inner_fast<8, KIND>>(grid, IP_NT, lds, st, a); break;
+    case 16: launch_lds<inner_fast<16, KIND>>(grid, IP_NT, lds, st, a); break;
+    case 32: launch_lds<inner_fast<32, KIND>>(grid, IP_NT, lds, st, a); break;
+    default: launch_lds<inner_fast<64, KIND>>(grid, IP_NT, lds, st, a); break;
   }
 }
 
@@ -471,21 +471,10 @@ static int launch_inner(InnerArgs a, hipStream_t st, const char* what, const Fie
     const size_t lds = (size_t)S * per;
     const unsigned grid = (unsigned)((a.batch + S - 1) / S);
     if (a.ids == nullptr) {
-      if (lds > 64 * 1024) {
-        static LdsAttr set[5];
-        const void* kern[5] = {(const void*)inner_fast<4, 3>, (const void*)inner_fast<8, 3>,
-                               (const void*)inner_fast<16, 3>, (const void*)inner_fast<32, 3>,
-                               (const void*)inner_fast<64, 3>};
-        const int ki = a.k == 4 ? 0 : a.k == 8 ? 1 : a.k == 16 ? 2 : a.k == 32 ? 3 : 4;
-        lds_attr(set[ki], kern[ki], lds);
-      }
       launch_inner_fast_k<3>(a, lds, grid, st);
     } else if (hm && a.k == 16 && a.F <= 32 && S == IP_SMAX) {
       with_id_kind(a.id_kind, [&](auto K) {
-        constexpr int KIND = decltype(K)::value;
-        static LdsAttr set[3];
-        lds_attr(set[KIND], (const void*)inner_fast_ka<KIND>, lds);
-        inner_fast_ka<KIND><<<grid, IP_NT, lds, st>>>(a, *hm);
+        launch_lds<inner_fast_ka<decltype(K)::value>>(grid, IP_NT, lds, st, a, *hm);
       });
     } else {
       with_id_kind(a.id_kind, [&](auto K) { launch_inner_fast_k<decltype(K)::value>(a, lds, grid, st); });
@@ -504,20 +493,10 @@ static int launch_inner(InnerArgs a, hipStream_t st, const char* what, const Fie
   a.S = S;
   const size_t lds = (size_t)S * per;
   const unsigned grid = (unsigned)((a.batch + S - 1) / S);
-  static LdsAttr set[4];
-  if (a.k <= 8) {
-    lds_attr(set[0], (const void*)inner_kernel<8>, lds);
-    inner_kernel<8><<<grid, 256, lds, st>>>(a);
-  } else if (a.k <= 16) {
-    lds_attr(set[1], (const void*)inner_kernel<16>, lds);
-    inner_kernel<16><<<grid, 256, lds, st>>>(a);
-  } else if (a.k <= 32) {
-    lds_attr(set[2], (const void*)inner_kernel<32>, lds);
-    inner_kernel<32><<<grid, 256, lds, st>>>(a);
-  } else {
-    lds_attr(set[3], (const void*)inner_kernel<64>, lds);
-    inner_kernel<64><<<grid, 256, lds, st>>>(a);
-  }
+  if (a.k <= 8) launch_lds<inner_kernel<8>>(grid, 256, lds, st, a);
+  else if (a.k <= 16) launch_lds<inner_kernel<16>>(grid, 256, lds, st, a);
+  else if (a.k <= 32) launch_lds<inner_kernel<32>>(grid, 256, lds, st, a);
+  else launch_lds<inner_kernel<64>>(grid, 256, lds, st, a);
   return launch_status(what);
 }
 
@@ -567,6 +546,73 @@ extern "C" int rs_outer_prepare(const float* W, int n_fields, int k, float* prep
 static unsigned long long* g_inner_dbg = nullptr;
 extern "C" void rs_diag_inner_set_dbg(unsigned long long* p) { g_inner_dbg = p; }
 
+namespace rs {
+// The entry points' arguments as an InnerArgs (everything else zero; S, NG and
+// contig: launch_inner).  out's columns are [flat F*k | inner P | outer P],
+// each part only when asked for (outer: outer_img non-null); rows come from
+// emb, or from the table when the caller adds ids (embed_inner_run).
+static InnerArgs inner_args(const float* emb, int F, int k, bool flat, bool inner, const float* outer_img, float* out,
+                            int64_t out_stride, int64_t batch) {
+  InnerArgs a{};
+  a.dbg = g_inner_dbg;
+  a.emb = emb;
+  a.F = F;
+  a.k = k;
+  a.out = out;
+  a.out_stride = out_stride;
+  a.write_flat = flat ? 1 : 0;
+  a.want_inner = inner ? 1 : 0;
+  a.inner_off = flat ? F * k : 0;
+  a.outer_img = outer_img;
+  a.outer_off = a.inner_off + (inner ? F * (F - 1) / 2 : 0);
+  a.batch = batch;
+  return a;
+}
+
+// The id entries' argument checks.  product: rs_embed_product_fwd's shape rule
+// (the fast kernel's shapes only); else rs_embed_inner_fwd's (any k <= 64,
+// inner part alone: the caller passes inner = 1 and no outer weights).
+static int check_inner(const char* what, bool product, const void* ids, int id_kind, const float* table,
+                       const int64_t* field_offsets, const int64_t* field_vocab, int n_fields, int k, int inner,
+                       const float* outer_prepared, const float* out, int64_t out_stride, int64_t batch) {
+  RS_REQUIRE(ids && table && field_offsets && field_vocab && out, "%s: null pointer", what);
+  if (product) {
+    RS_REQUIRE(inner || outer_prepared, "%s: nothing to compute (inner=0, no outer weights)", what);
+    RS_REQUIRE(n_fields <= IP_FMAX && rs_outer_prepared_size(n_fields, k) > 0,
+               "%s: need 2..%d fields and k in {4,8,16,32,64}", what, IP_FMAX);
+    RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32 && batch >= 0, "%s: bad ids", what);
+  } else {
+    RS_REQUIRE(n_fields >= 1 && k >= 1 && k <= 64 && batch >= 0, "%s: bad shape (k<=64)", what);
+    RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "%s: bad id_kind", what);
+  }
+  const int64_t P = (int64_t)n_fields * (n_fields - 1) / 2;
+  RS_REQUIRE(out_stride >= (int64_t)n_fields * k + (inner ? P : 0) + (outer_prepared ? P : 0),
+             "%s: out_stride too small", what);
+  RS_REQUIRE(k % 4 != 0 || (uintptr_t)table % 16 == 0, "%s: table must be 16-B aligned", what);
+  return RS_OK;
+}
+
+// rs_embed_inner_fwd[_hm] (product = false, inner = 1, no outer weights) and
+// rs_embed_product_fwd[_hm]; hm: kernarg_meta of the host metadata, or null.
+static int embed_inner_run(const char* what, bool product, const void* ids, int id_kind, int64_t id_stride,
+                           const float* table, const int64_t* field_offsets, const int64_t* field_vocab, int n_fields,
+                           int k, int inner, const float* outer_prepared, float* out, int64_t out_stride,
+                           int64_t batch, int* err_flag, rs_stream_t stream, const FieldMeta* hm) {
+  if (const int rc = check_inner(what, product, ids, id_kind, table, field_offsets, field_vocab, n_fields, k, inner,
+                                 outer_prepared, out, out_stride, batch))
+    return rc;
+  InnerArgs a = inner_args(nullptr, n_fields, k, true, inner, outer_prepared, out, out_stride, batch);
+  a.ids = ids;
+  a.id_kind = id_kind;
+  a.id_stride = id_stride;
+  a.table = table;
+  a.offs = field_offsets;
+  a.vocab = field_vocab;
+  a.err = err_flag;
+  return launch_inner(a, as_stream(stream), what, hm);
+}
+}  // namespace rs
+
 extern "C" int rs_inner_product_fwd(const float* emb, int n_fields, int k, float* out, int64_t out_stride,
                                     int64_t batch, rs_stream_t stream) {
   if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
@@ -574,31 +620,9 @@ extern "C" int rs_inner_product_fwd(const float* emb, int n_fields, int k, float
   RS_REQUIRE(n_fields >= 1 && k >= 1 && k <= 64 && batch >= 0, "rs_inner_product_fwd: bad shape (k<=64)");
   RS_REQUIRE(out_stride >= (int64_t)n_fields * (n_fields - 1) / 2, "rs_inner_product_fwd: out_stride too small");
   RS_REQUIRE(k % 4 != 0 || (uintptr_t)emb % 16 == 0, "rs_inner_product_fwd: emb must be 16-B aligned");
-  InnerArgs a{};
-  a.dbg = g_inner_dbg;
-  a.emb = emb;
-  a.F = n_fields;
-  a.k = k;
-  a.out = out;
-  a.out_stride = out_stride;
-  a.inner_off = 0;
-  a.write_flat = 0;
-  a.want_inner = 1;
-  a.batch = batch;
-  return launch_inner(a, as_stream(stream), "rs_inner_product_fwd");
+  return launch_inner(inner_args(emb, n_fields, k, false, true, nullptr, out, out_stride, batch), as_stream(stream),
+                      "rs_inner_product_fwd");
 }
-
-namespace rs {
-static const FieldMeta* inner_host_meta(FieldMeta& m, const int64_t* off_h, const int64_t* voc_h, int n_fields,
-                                        int k) {
-  if (!off_h || !voc_h || k != 16 || n_fields < 1 || n_fields > 32) return nullptr;
-  for (int c = 0; c < n_fields; ++c) {
-    m.off[c] = off_h[c];
-    m.voc[c] = voc_h[c];
-  }
-  return &m;
-}
-}  // namespace rs
 
 extern "C" int rs_embed_inner_fwd_hm(const void* ids, int id_kind, int64_t id_stride, const float* table,
                                      const int64_t* field_offsets, const int64_t* field_vocab,
@@ -607,32 +631,10 @@ extern "C" int rs_embed_inner_fwd_hm(const void* ids, int id_kind, int64_t id_st
                                      int* err_flag, rs_stream_t stream) {
   if (batch == 0) return RS_OK;
   RS_REQUIRE(field_offsets_host && field_vocab_host, "rs_embed_inner_fwd_hm: host metadata missing");
-  RS_REQUIRE(ids && table && field_offsets && field_vocab && out, "rs_embed_inner_fwd_hm: null pointer");
-  RS_REQUIRE(n_fields >= 1 && k >= 1 && k <= 64 && batch >= 0, "rs_embed_inner_fwd_hm: bad shape (k<=64)");
-  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_embed_inner_fwd_hm: bad id_kind");
-  RS_REQUIRE(out_stride >= (int64_t)n_fields * k + (int64_t)n_fields * (n_fields - 1) / 2,
-             "rs_embed_inner_fwd_hm: out_stride too small");
-  RS_REQUIRE(k % 4 != 0 || (uintptr_t)table % 16 == 0, "rs_embed_inner_fwd_hm: table must be 16-B aligned");
-  InnerArgs a{};
-  a.dbg = g_inner_dbg;
-  a.ids = ids;
-  a.id_kind = id_kind;
-  a.id_stride = id_stride;
-  a.table = table;
-  a.offs = field_offsets;
-  a.vocab = field_vocab;
-  a.F = n_fields;
-  a.k = k;
-  a.out = out;
-  a.out_stride = out_stride;
-  a.inner_off = n_fields * k;
-  a.write_flat = 1;
-  a.want_inner = 1;
-  a.batch = batch;
-  a.err = err_flag;
   FieldMeta m;
-  return launch_inner(a, as_stream(stream), "rs_embed_inner_fwd_hm",
-                      inner_host_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
+  return embed_inner_run("rs_embed_inner_fwd_hm", false, ids, id_kind, id_stride, table, field_offsets, field_vocab,
+                         n_fields, k, 1, nullptr, out, out_stride, batch, err_flag, stream,
+                         kernarg_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
 }
 
 extern "C" int rs_embed_product_fwd_hm(const void* ids, int id_kind, int64_t id_stride, const float* table,
@@ -642,37 +644,10 @@ extern "C" int rs_embed_product_fwd_hm(const void* ids, int id_kind, int64_t id_
                                        int64_t out_stride, int64_t batch, int* err_flag, rs_stream_t stream) {
   if (batch == 0) return RS_OK;
   RS_REQUIRE(field_offsets_host && field_vocab_host, "rs_embed_product_fwd_hm: host metadata missing");
-  RS_REQUIRE(ids && table && field_offsets && field_vocab && out, "rs_embed_product_fwd_hm: null pointer");
-  RS_REQUIRE(inner || outer_prepared, "rs_embed_product_fwd_hm: nothing to compute (inner=0, no outer weights)");
-  RS_REQUIRE(n_fields <= IP_FMAX && rs_outer_prepared_size(n_fields, k) > 0,
-             "rs_embed_product_fwd_hm: need 2..%d fields and k in {4,8,16,32,64}", IP_FMAX);
-  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32 && batch >= 0, "rs_embed_product_fwd_hm: bad ids");
-  const int P = n_fields * (n_fields - 1) / 2;
-  RS_REQUIRE(out_stride >= (int64_t)n_fields * k + (inner ? P : 0) + (outer_prepared ? P : 0),
-             "rs_embed_product_fwd_hm: out_stride too small");
-  RS_REQUIRE((uintptr_t)table % 16 == 0, "rs_embed_product_fwd_hm: table must be 16-B aligned");
-  InnerArgs a{};
-  a.dbg = g_inner_dbg;
-  a.ids = ids;
-  a.id_kind = id_kind;
-  a.id_stride = id_stride;
-  a.table = table;
-  a.offs = field_offsets;
-  a.vocab = field_vocab;
-  a.F = n_fields;
-  a.k = k;
-  a.out = out;
-  a.out_stride = out_stride;
-  a.write_flat = 1;
-  a.want_inner = inner ? 1 : 0;
-  a.inner_off = n_fields * k;
-  a.outer_img = outer_prepared;
-  a.outer_off = n_fields * k + (inner ? P : 0);
-  a.batch = batch;
-  a.err = err_flag;
   FieldMeta m;
-  return launch_inner(a, as_stream(stream), "rs_embed_product_fwd_hm",
-                      inner_host_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
+  return embed_inner_run("rs_embed_product_fwd_hm", true, ids, id_kind, id_stride, table, field_offsets, field_vocab,
+                         n_fields, k, inner, outer_prepared, out, out_stride, batch, err_flag, stream,
+                         kernarg_meta(m, field_offsets_host, field_vocab_host, n_fields, k));
 }
 
 extern "C" int rs_embed_inner_fwd(const void* ids, int id_kind, int64_t id_stride, const float* table,
@@ -680,30 +655,8 @@ extern "C" int rs_embed_inner_fwd(const void* ids, int id_kind, int64_t id_strid
                                   float* out, int64_t out_stride, int64_t batch, int* err_flag,
                                   rs_stream_t stream) {
   if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
-  RS_REQUIRE(ids && table && field_offsets && field_vocab && out, "rs_embed_inner_fwd: null pointer");
-  RS_REQUIRE(n_fields >= 1 && k >= 1 && k <= 64 && batch >= 0, "rs_embed_inner_fwd: bad shape (k<=64)");
-  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_embed_inner_fwd: bad id_kind");
-  RS_REQUIRE(out_stride >= (int64_t)n_fields * k + (int64_t)n_fields * (n_fields - 1) / 2,
-             "rs_embed_inner_fwd: out_stride too small");
-  RS_REQUIRE(k % 4 != 0 || (uintptr_t)table % 16 == 0, "rs_embed_inner_fwd: table must be 16-B aligned");
-  InnerArgs a{};
-  a.dbg = g_inner_dbg;
-  a.ids = ids;
-  a.id_kind = id_kind;
-  a.id_stride = id_stride;
-  a.table = table;
-  a.offs = field_offsets;
-  a.vocab = field_vocab;
-  a.F = n_fields;
-  a.k = k;
-  a.out = out;
-  a.out_stride = out_stride;
-  a.inner_off = n_fields * k;
-  a.write_flat = 1;
-  a.want_inner = 1;
-  a.batch = batch;
-  a.err = err_flag;
-  return launch_inner(a, as_stream(stream), "rs_embed_inner_fwd");
+  return embed_inner_run("rs_embed_inner_fwd", false, ids, id_kind, id_stride, table, field_offsets, field_vocab,
+                         n_fields, k, 1, nullptr, out, out_stride, batch, err_flag, stream, nullptr);
 }
 
 extern "C" int rs_embed_product_fwd(const void* ids, int id_kind, int64_t id_stride, const float* table,
@@ -711,35 +664,8 @@ extern "C" int rs_embed_product_fwd(const void* ids, int id_kind, int64_t id_str
                                     int inner, const float* outer_prepared, float* out, int64_t out_stride,
                                     int64_t batch, int* err_flag, rs_stream_t stream) {
   if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
-  RS_REQUIRE(ids && table && field_offsets && field_vocab && out, "rs_embed_product_fwd: null pointer");
-  RS_REQUIRE(inner || outer_prepared, "rs_embed_product_fwd: nothing to compute (inner=0, no outer weights)");
-  RS_REQUIRE(n_fields <= IP_FMAX && rs_outer_prepared_size(n_fields, k) > 0,
-             "rs_embed_product_fwd: need 2..%d fields and k in {4,8,16,32,64}", IP_FMAX);
-  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32 && batch >= 0, "rs_embed_product_fwd: bad ids");
-  const int P = n_fields * (n_fields - 1) / 2;
-  RS_REQUIRE(out_stride >= (int64_t)n_fields * k + (inner ? P : 0) + (outer_prepared ? P : 0),
-             "rs_embed_product_fwd: out_stride too small");
-  RS_REQUIRE((uintptr_t)table % 16 == 0, "rs_embed_product_fwd: table must be 16-B aligned");
-  InnerArgs a{};
-  a.dbg = g_inner_dbg;
-  a.ids = ids;
-  a.id_kind = id_kind;
-  a.id_stride = id_stride;
-  a.table = table;
-  a.offs = field_offsets;
-  a.vocab = field_vocab;
-  a.F = n_fields;
-  a.k = k;
-  a.out = out;
-  a.out_stride = out_stride;
-  a.write_flat = 1;
-  a.want_inner = inner ? 1 : 0;
-  a.inner_off = n_fields * k;
-  a.outer_img = outer_prepared;
-  a.outer_off = n_fields * k + (inner ? P : 0);
-  a.batch = batch;
-  a.err = err_flag;
-  return launch_inner(a, as_stream(stream), "rs_embed_product_fwd");
+  return embed_inner_run("rs_embed_product_fwd", true, ids, id_kind, id_stride, table, field_offsets, field_vocab,
+                         n_fields, k, inner, outer_prepared, out, out_stride, batch, err_flag, stream, nullptr);
 }
 
 extern "C" int rs_outer_product_fwd(const float* emb, int n_fields, int k, const float* outer_prepared, float* out,
@@ -751,18 +677,8 @@ extern "C" int rs_outer_product_fwd(const float* emb, int n_fields, int k, const
   RS_REQUIRE(out_stride >= (int64_t)n_fields * (n_fields - 1) / 2 && batch >= 0,
              "rs_outer_product_fwd: out_stride too small");
   RS_REQUIRE((uintptr_t)emb % 16 == 0, "rs_outer_product_fwd: emb must be 16-B aligned");
-  InnerArgs a{};
-  a.dbg = g_inner_dbg;
-  a.emb = emb;
-  a.F = n_fields;
-  a.k = k;
-  a.out = out;
-  a.out_stride = out_stride;
-  a.want_inner = 0;
-  a.outer_img = outer_prepared;
-  a.outer_off = 0;
-  a.batch = batch;
-  return launch_inner(a, as_stream(stream), "rs_outer_product_fwd");
+  return launch_inner(inner_args(emb, n_fields, k, false, false, outer_prepared, out, out_stride, batch),
+                      as_stream(stream), "rs_outer_product_fwd");
 }
 
 // [flat | inner | outer] from given embeddings (model/pnn.py:37-48 on z =
@@ -778,18 +694,6 @@ extern "C" int rs_product_fwd(const float* emb, int n_fields, int k, int inner, 
   RS_REQUIRE(batch >= 0 && out_stride >= (int64_t)n_fields * k + (inner ? P : 0) + (outer_prepared ? P : 0),
              "rs_product_fwd: out_stride too small");
   RS_REQUIRE((uintptr_t)emb % 16 == 0, "rs_product_fwd: emb must be 16-B aligned");
-  InnerArgs a{};
-  a.dbg = g_inner_dbg;
-  a.emb = emb;
-  a.F = n_fields;
-  a.k = k;
-  a.out = out;
-  a.out_stride = out_stride;
-  a.write_flat = 1;
-  a.want_inner = inner ? 1 : 0;
-  a.inner_off = n_fields * k;
-  a.outer_img = outer_prepared;
-  a.outer_off = n_fields * k + (inner ? P : 0);
-  a.batch = batch;
-  return launch_inner(a, as_stream(stream), "rs_product_fwd");
+  return launch_inner(inner_args(emb, n_fields, k, true, inner, outer_prepared, out, out_stride, batch),
+                      as_stream(stream), "rs_product_fwd");
 }

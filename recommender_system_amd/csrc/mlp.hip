@@ -214,27 +214,14 @@ static int mlp_run(const float* x, int64_t x_stride, const float* in_scale, cons
   RS_REQUIRE(grid < (1ll << 31), "rs_mlp_fwd: batch too large");
   int gwa = 0, gwb = 0;
   const bool tail = MLP_NW == 16 && mlp_tail_ok(a.Np, a.Kp, a.N, a.L, 1, gwa, gwb) && gwa == 8 && gwb == 2;
+  hipStream_t st = as_stream(stream);
   if (pc) {
-    if (tail) {
-      static LdsAttr lds_pt;
-      lds_attr(lds_pt, (const void*)mlp_tower_pc<MLP_NW, true>, lds);
-      mlp_tower_pc<MLP_NW, true><<<(unsigned)grid, MLP_NW * 64, lds, as_stream(stream)>>>(a, *pc);
-    } else {
-      static LdsAttr lds_p;
-      lds_attr(lds_p, (const void*)mlp_tower_pc<MLP_NW>, lds);
-      mlp_tower_pc<MLP_NW><<<(unsigned)grid, MLP_NW * 64, lds, as_stream(stream)>>>(a, *pc);
-    }
+    if (tail) launch_lds<mlp_tower_pc<MLP_NW, true>>((unsigned)grid, MLP_NW * 64, lds, st, a, *pc);
+    else launch_lds<mlp_tower_pc<MLP_NW>>((unsigned)grid, MLP_NW * 64, lds, st, a, *pc);
     return launch_status("rs_mlp_affine_pieces_fwd");
   }
-  if (tail) {
-    static LdsAttr lds_tail;
-    lds_attr(lds_tail, (const void*)mlp_tower<MLP_NW, true>, lds);
-    mlp_tower<MLP_NW, true><<<(unsigned)grid, MLP_NW * 64, lds, as_stream(stream)>>>(a);
-    return launch_status("rs_mlp_fwd");
-  }
-  static LdsAttr lds_set;  // opt in to exactly what is needed beyond the default
-  lds_attr(lds_set, (const void*)mlp_tower<MLP_NW>, lds);
-  mlp_tower<MLP_NW><<<(unsigned)grid, MLP_NW * 64, lds, as_stream(stream)>>>(a);
+  if (tail) launch_lds<mlp_tower<MLP_NW, true>>((unsigned)grid, MLP_NW * 64, lds, st, a);
+  else launch_lds<mlp_tower<MLP_NW>>((unsigned)grid, MLP_NW * 64, lds, st, a);
   return launch_status("rs_mlp_fwd");
 }
 

@@ -365,9 +365,7 @@ template <int KIND, bool SAVE = false>
 static int res_launch(const ResArgs& a, const ResGeom& g, rs_stream_t stream, const char* what) {
   const int64_t grid = (a.M + 15) / 16;
   RS_REQUIRE(grid < (1ll << 31), "%s: batch too large", what);
-  static LdsAttr lds_set;
-  lds_attr(lds_set, (const void*)res_tower<RES_NW, KIND, SAVE>, g.lds);
-  res_tower<RES_NW, KIND, SAVE><<<(unsigned)grid, RES_NW * 64, g.lds, as_stream(stream)>>>(a);
+  launch_lds<res_tower<RES_NW, KIND, SAVE>>((unsigned)grid, RES_NW * 64, g.lds, as_stream(stream), a);
   return launch_status(what);
 }
 
@@ -600,6 +598,27 @@ extern "C" int rs_res_tower_prepare(int d, int n_hidden, const int* hidden, int 
   return launch_status("rs_res_tower_prepare");
 }
 
+static void res_fill_saved(int d, int n_hidden, const int* hidden, float* saved, float* logit, ResArgs& a) {
+  const ResSaved s = res_saved(d, n_hidden, hidden);
+  for (int l = 0; l <= n_hidden; ++l) a.N[l] = s.N[l];
+  a.sw = s.sw;
+  a.saved = saved;
+  a.logit = logit;
+}
+
+// rs_res_tower_fwd / rs_res_tower_train_fwd: the checks of the given rows x
+// (outs: every output pointer the entry needs is there) and their ResArgs.
+static int res_x_source(const char* what, const ResGeom& g, const float* prepared, const float* x, int64_t x_stride,
+                        bool outs, int64_t batch, ResArgs& a) {
+  RS_REQUIRE(x && prepared && outs, "%s: null pointer", what);
+  RS_REQUIRE(batch >= 0 && x_stride >= g.d, "%s: bad batch/stride (x_stride < d)", what);
+  res_fill_args(g, prepared, a);
+  a.x = x;
+  a.xs = x_stride;
+  a.M = batch;
+  return RS_OK;
+}
+
 extern "C" int rs_res_tower_fwd(const float* x, int64_t x_stride, int d, int n_hidden, const int* hidden,
                                 int n_units, const float* prepared, int head, float* y, int64_t y_stride,
                                 int64_t batch, rs_stream_t stream) {
@@ -607,13 +626,9 @@ extern "C" int rs_res_tower_fwd(const float* x, int64_t x_stride, int d, int n_h
   ResGeom g;
   RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, head, g), "rs_res_tower_fwd: " RES_SHAPE_MSG " (head 0 or 1)",
              RES_MAXH, RES_MAXU, MLP_MAXD);
-  RS_REQUIRE(x && prepared && y, "rs_res_tower_fwd: null pointer");
-  RS_REQUIRE(batch >= 0 && x_stride >= d, "rs_res_tower_fwd: bad batch/stride (x_stride < d)");
-  RS_REQUIRE(y_stride >= (head ? 1 : d), "rs_res_tower_fwd: y_stride too small");
   ResArgs a{};
-  res_fill_args(g, prepared, a);
-  a.x = x;
-  a.xs = x_stride;
+  if (const int rc = res_x_source("rs_res_tower_fwd", g, prepared, x, x_stride, y != nullptr, batch, a)) return rc;
+  RS_REQUIRE(y_stride >= (head ? 1 : d), "rs_res_tower_fwd: y_stride too small");
   if (head) {
     a.yh = y;
     a.yhs = y_stride;
@@ -621,31 +636,35 @@ extern "C" int rs_res_tower_fwd(const float* x, int64_t x_stride, int d, int n_h
     a.xl = y;
     a.xls = y_stride;
   }
-  a.M = batch;
   return res_launch<3>(a, g, stream, "rs_res_tower_fwd");
 }
 
-extern "C" int rs_deepcrossing_fwd(const void* ids, int id_kind, int64_t id_stride, const float* dense,
-                                   int64_t dense_stride, int nd, const float* table, const int64_t* field_offsets,
-                                   const int64_t* field_vocab, int n_fields, int k, int n_hidden, const int* hidden,
-                                   int n_units, const float* prepared, float* out, float* x_last,
-                                   int64_t x_last_stride, int64_t batch, int* err_flag, rs_stream_t stream) {
-  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+// rs_deepcrossing_fwd (saved = logit = null: inference, x_last optional) and
+// rs_deepcrossing_train_fwd (both given, no x_last): the checks, the id source
+// of the ResArgs and the launch.
+static int deepcrossing_run(const char* what, bool train, const void* ids, int id_kind, int64_t id_stride,
+                            const float* dense, int64_t dense_stride, int nd, const float* table,
+                            const int64_t* field_offsets, const int64_t* field_vocab, int n_fields, int k,
+                            int n_hidden, const int* hidden, int n_units, const float* prepared, float* saved,
+                            float* out, float* logit, float* x_last, int64_t x_last_stride, int64_t batch,
+                            int* err_flag, rs_stream_t stream) {
   RS_REQUIRE(batch >= 0 && nd >= 0 && n_fields >= 1 && k >= 1 && n_fields <= MLP_MAXD && k <= MLP_MAXD,
-             "rs_deepcrossing_fwd: bad shape");
+             "%s: bad shape", what);
   const int d = nd + n_fields * k;
   ResGeom g;
-  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, 1, g),
-             "rs_deepcrossing_fwd: " RES_SHAPE_MSG " (input width nd + n_fields * k)", RES_MAXH, RES_MAXU, MLP_MAXD);
-  RS_REQUIRE(ids && table && field_offsets && field_vocab && prepared && out && (nd == 0 || dense),
-             "rs_deepcrossing_fwd: null pointer");
-  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_deepcrossing_fwd: bad id_kind");
+  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, 1, g), "%s: " RES_SHAPE_MSG " (input width nd + n_fields * k)",
+             what, RES_MAXH, RES_MAXU, MLP_MAXD);
+  RS_REQUIRE(ids && table && field_offsets && field_vocab && prepared && out && (!train || (saved && logit)) &&
+                 (nd == 0 || dense),
+             "%s: null pointer", what);
+  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "%s: bad id_kind", what);
   RS_REQUIRE(id_stride >= n_fields && (nd == 0 || dense_stride >= nd),
-             "rs_deepcrossing_fwd: id_stride / dense_stride smaller than the width");
-  RS_REQUIRE(!x_last || x_last_stride >= d, "rs_deepcrossing_fwd: x_last_stride too small");
-  RS_REQUIRE((uintptr_t)table % 16 == 0, "rs_deepcrossing_fwd: table must be 16-B aligned");
+             "%s: id_stride / dense_stride smaller than the width", what);
+  RS_REQUIRE(!x_last || x_last_stride >= d, "%s: x_last_stride too small", what);
+  RS_REQUIRE((uintptr_t)table % 16 == 0, "%s: table must be 16-B aligned", what);
   ResArgs a{};
   res_fill_args(g, prepared, a);
+  if (train) res_fill_saved(d, n_hidden, hidden, saved, logit, a);
   a.ids = ids;
   a.id_stride = id_stride;
   a.dense = dense;
@@ -663,8 +682,22 @@ extern "C" int rs_deepcrossing_fwd(const void* ids, int id_kind, int64_t id_stri
   a.yhs = 1;
   a.M = batch;
   int st = RS_OK;
-  with_id_kind(id_kind, [&](auto K) { st = res_launch<decltype(K)::value>(a, g, stream, "rs_deepcrossing_fwd"); });
+  with_id_kind(id_kind, [&](auto K) {
+    constexpr int KIND = decltype(K)::value;
+    st = train ? res_launch<KIND, true>(a, g, stream, what) : res_launch<KIND>(a, g, stream, what);
+  });
   return st;
+}
+
+extern "C" int rs_deepcrossing_fwd(const void* ids, int id_kind, int64_t id_stride, const float* dense,
+                                   int64_t dense_stride, int nd, const float* table, const int64_t* field_offsets,
+                                   const int64_t* field_vocab, int n_fields, int k, int n_hidden, const int* hidden,
+                                   int n_units, const float* prepared, float* out, float* x_last,
+                                   int64_t x_last_stride, int64_t batch, int* err_flag, rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  return deepcrossing_run("rs_deepcrossing_fwd", false, ids, id_kind, id_stride, dense, dense_stride, nd, table,
+                          field_offsets, field_vocab, n_fields, k, n_hidden, hidden, n_units, prepared, nullptr, out,
+                          nullptr, x_last, x_last_stride, batch, err_flag, stream);
 }
 
 // ------------------------------------------------------------------ training
@@ -677,14 +710,6 @@ extern "C" int64_t rs_res_tower_saved_size(int d, int n_hidden, const int* hidde
   return batch * (d + n_units * res_saved(d, n_hidden, hidden).sw);
 }
 
-static void res_fill_saved(int d, int n_hidden, const int* hidden, float* saved, float* logit, ResArgs& a) {
-  const ResSaved s = res_saved(d, n_hidden, hidden);
-  for (int l = 0; l <= n_hidden; ++l) a.N[l] = s.N[l];
-  a.sw = s.sw;
-  a.saved = saved;
-  a.logit = logit;
-}
-
 extern "C" int rs_res_tower_train_fwd(const float* x, int64_t x_stride, int d, int n_hidden, const int* hidden,
                                       int n_units, const float* prepared, float* saved, float* out, float* logit,
                                       int64_t batch, rs_stream_t stream) {
@@ -692,16 +717,13 @@ extern "C" int rs_res_tower_train_fwd(const float* x, int64_t x_stride, int d, i
   ResGeom g;
   RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, 1, g), "rs_res_tower_train_fwd: " RES_SHAPE_MSG, RES_MAXH,
              RES_MAXU, MLP_MAXD);
-  RS_REQUIRE(x && prepared && saved && out && logit, "rs_res_tower_train_fwd: null pointer");
-  RS_REQUIRE(batch >= 0 && x_stride >= d, "rs_res_tower_train_fwd: bad batch/stride (x_stride < d)");
   ResArgs a{};
-  res_fill_args(g, prepared, a);
+  if (const int rc =
+          res_x_source("rs_res_tower_train_fwd", g, prepared, x, x_stride, saved && out && logit, batch, a))
+    return rc;
   res_fill_saved(d, n_hidden, hidden, saved, logit, a);
-  a.x = x;
-  a.xs = x_stride;
   a.yh = out;
   a.yhs = 1;
-  a.M = batch;
   return res_launch<3, true>(a, g, stream, "rs_res_tower_train_fwd");
 }
 
@@ -712,41 +734,9 @@ extern "C" int rs_deepcrossing_train_fwd(const void* ids, int id_kind, int64_t i
                                          float* saved, float* out, float* logit, int64_t batch, int* err_flag,
                                          rs_stream_t stream) {
   if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
-  RS_REQUIRE(batch >= 0 && nd >= 0 && n_fields >= 1 && k >= 1 && n_fields <= MLP_MAXD && k <= MLP_MAXD,
-             "rs_deepcrossing_train_fwd: bad shape");
-  const int d = nd + n_fields * k;
-  ResGeom g;
-  RS_REQUIRE(res_geom(d, n_hidden, hidden, n_units, 1, g),
-             "rs_deepcrossing_train_fwd: " RES_SHAPE_MSG " (input width nd + n_fields * k)", RES_MAXH, RES_MAXU,
-             MLP_MAXD);
-  RS_REQUIRE(ids && table && field_offsets && field_vocab && prepared && saved && out && logit && (nd == 0 || dense),
-             "rs_deepcrossing_train_fwd: null pointer");
-  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_deepcrossing_train_fwd: bad id_kind");
-  RS_REQUIRE(id_stride >= n_fields && (nd == 0 || dense_stride >= nd),
-             "rs_deepcrossing_train_fwd: id_stride / dense_stride smaller than the width");
-  RS_REQUIRE((uintptr_t)table % 16 == 0, "rs_deepcrossing_train_fwd: table must be 16-B aligned");
-  ResArgs a{};
-  res_fill_args(g, prepared, a);
-  res_fill_saved(d, n_hidden, hidden, saved, logit, a);
-  a.ids = ids;
-  a.id_stride = id_stride;
-  a.dense = dense;
-  a.dense_stride = dense_stride;
-  a.nd = nd;
-  a.table = table;
-  a.offs = field_offsets;
-  a.vocab = field_vocab;
-  a.F = n_fields;
-  a.k = k;
-  a.err = err_flag;
-  a.yh = out;
-  a.yhs = 1;
-  a.M = batch;
-  int st = RS_OK;
-  with_id_kind(id_kind, [&](auto K) {
-    st = res_launch<decltype(K)::value, true>(a, g, stream, "rs_deepcrossing_train_fwd");
-  });
-  return st;
+  return deepcrossing_run("rs_deepcrossing_train_fwd", true, ids, id_kind, id_stride, dense, dense_stride, nd, table,
+                          field_offsets, field_vocab, n_fields, k, n_hidden, hidden, n_units, prepared, saved, out,
+                          logit, nullptr, 0, batch, err_flag, stream);
 }
 
 extern "C" int64_t rs_res_tower_bwd_prepared_size(int d, int n_hidden, const int* hidden, int n_units) {
@@ -823,8 +813,6 @@ extern "C" int rs_res_tower_bwd(const float* saved, int d, int n_hidden, const i
   a.head_off = gm.head_off;
   a.unroll = opt(RS_OPT_MLP_UNROLL);
   a.M = batch;
-  static LdsAttr lds_set;
-  lds_attr(lds_set, (const void*)res_tower_bwd<RES_NW>, gm.lds);
-  res_tower_bwd<RES_NW><<<(unsigned)grid, RES_NW * 64, gm.lds, as_stream(stream)>>>(a);
+  launch_lds<res_tower_bwd<RES_NW>>((unsigned)grid, RES_NW * 64, gm.lds, as_stream(stream), a);
   return launch_status("rs_res_tower_bwd");
 }

@@ -20,10 +20,10 @@ int launch_status(const char* what);
 
 inline hipStream_t as_stream(rs_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-// A kernel's dynamic-LDS opt-in (hipFuncSetAttribute) beyond the 64 KiB
-// default, per device: set[d] = the largest size set so far on device d (only
-// successful calls are recorded; a failure is retried at the next launch,
-// whose own launch status then reports it).
+// A kernel's dynamic-LDS opt-in beyond the 64 KiB default, per device:
+// set[d] = the largest size set so far on device d (only successful calls are
+// recorded; a failure is retried at the next launch, whose own launch status
+// then reports it).  Launch through launch_lds, which owns the state.
 struct LdsAttr {
   size_t set[64] = {};
 };
@@ -33,6 +33,15 @@ inline void lds_attr(LdsAttr& s, const void* kern, size_t lds) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   if (lds <= s.set[dev]) return;
   if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) s.set[dev] = lds;
+}
+// Launch KERN with lds bytes of dynamic LDS, opted in first: every launch
+// whose LDS size can exceed 64 KiB goes through here, so the kernel is named
+// once and no site can forget the opt-in.
+template <auto KERN, class... A>
+inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  static LdsAttr set;  // one per kernel instantiation
+  lds_attr(set, (const void*)KERN, lds);
+  KERN<<<grid, block, lds, st>>>(args...);
 }
 
 #define RS_REQUIRE(cond, ...)            \

@@ -672,15 +672,14 @@ extern "C" int rs_shard_dedup_route(const void* ids, int id_kind, int64_t id_str
     int32_t* strad = reinterpret_cast<int32_t*>(ws + w.strad);
     with_id_kind(id_kind, [&](auto K) {
       constexpr int KI = decltype(K)::value;
-      auto go = [&](auto kern) {
-        static LdsAttr lds_set[3][3];
-        lds_attr(lds_set[KI][LW], (const void*)kern, lds);
-        kern<<<n_fields, T, lds, st>>>(ids, id_stride, field_offsets, field_vocab, n_fields, batch, rows_per_rank,
-                                       world, key_in, val_in, cnt, strad, err_flag, ws + w.incl);
+      auto go = [&](auto W) {
+        launch_lds<dedup_field_hash<KI, decltype(W)::value>>(n_fields, T, lds, st, ids, id_stride, field_offsets,
+                                                             field_vocab, n_fields, batch, rows_per_rank, world,
+                                                             key_in, val_in, cnt, strad, err_flag, ws + w.incl);
       };
-      if (LW == 0) go(dedup_field_hash<KI, 0>);
-      else if (LW == 1) go(dedup_field_hash<KI, 1>);
-      else go(dedup_field_hash<KI, 2>);
+      if (LW == 0) go(std::integral_constant<int, 0>());
+      else if (LW == 1) go(std::integral_constant<int, 1>());
+      else go(std::integral_constant<int, 2>());
     });
     const int64_t work = n > (int64_t)world * cap ? n : (int64_t)world * cap;
     dedup_scatter_f<<<(unsigned)((work + 255) / 256), 256, 0, st>>>(key_in, val_in, cnt, strad, field_offsets,
@@ -739,14 +738,10 @@ extern "C" int rs_shard_dedup_grad(const float* grad, int64_t grad_stride, int n
     const int32_t* cnt = reinterpret_cast<const int32_t*>(ws + w.fmeta);
     uint32_t* ko = reinterpret_cast<uint32_t*>(ws + w.key_out);
     int32_t* vo = reinterpret_cast<int32_t*>(ws + w.val_out);
-    auto go = [&](auto kern) {
-      static LdsAttr lds_set[3];
-      lds_attr(lds_set[LW], (const void*)kern, lds);
-      kern<<<n_fields, N2 / DH_KPL, lds, st>>>(rowg, fuh, n_fields, batch, cnt, ko, vo);
-    };
-    if (LW == 0) go(dedup_group_f<0>);
-    else if (LW == 1) go(dedup_group_f<1>);
-    else go(dedup_group_f<2>);
+    const unsigned T = N2 / DH_KPL;
+    if (LW == 0) launch_lds<dedup_group_f<0>>(n_fields, T, lds, st, rowg, fuh, n_fields, batch, cnt, ko, vo);
+    else if (LW == 1) launch_lds<dedup_group_f<1>>(n_fields, T, lds, st, rowg, fuh, n_fields, batch, cnt, ko, vo);
+    else launch_lds<dedup_group_f<2>>(n_fields, T, lds, st, rowg, fuh, n_fields, batch, cnt, ko, vo);
   }
   const unsigned g = (unsigned)((n * k + 255) / 256);
   dedup_grad_piece<<<g, 256, 0, st>>>(key, val, n, n_fields, k, grad, grad_stride, slot_of, C, part_first, part_last,

@@ -72,6 +72,52 @@ def test_signature_arity_matches_header():
         assert len(_lib.SIGNATURES[name][1]) == n, f"{name}: header has {n} params"
 
 
+_SCALAR = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "uint64_t": C.c_uint64,
+           "rs_stream_t": C.c_void_p, "void": None}
+_POINTEE = {"void", "char", "int", "float", "int32_t", "uint32_t", "int64_t", "uint64_t", "unsigned long long"}
+
+
+def _ctype(decl, named):
+    """The ctypes class of one C declaration: a parameter (`named`: its last
+    word is the parameter's name) or a return type.  An unknown type name
+    raises."""
+    decl = decl.strip()
+    if "*" in decl:
+        base = " ".join(w for w in decl[:decl.index("*")].split() if w != "const")
+        if base not in _POINTEE:
+            raise KeyError(f"unknown pointee type {base!r} in {decl!r}")
+        const_char = decl.replace(" ", "").startswith("constchar*") and decl.count("*") == 1
+        return C.c_char_p if const_char else C.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if named and len(words) > 1:
+        words = words[:-1]
+    base = " ".join(words)
+    if base not in _SCALAR:
+        raise KeyError(f"unknown type {base!r} in {decl!r}")
+    return _SCALAR[base]
+
+
+def test_signature_types_match_header():
+    """Every prototype's return type and each parameter's class (pointer /
+    int / int64 / float / uint64 / C string) equal the ctypes table's: an int
+    bound where the header says int64_t passes the arity test above."""
+    txt = _headers_text()
+    seen = 0
+    for m in re.finditer(r"^[ \t]*([A-Za-z_][\w \t\*]*?)[ \t]*\b(rs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt, flags=re.M):
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        if ret.split()[0] in ("typedef", "return"):
+            continue
+        want_res = _ctype(ret, named=False)
+        want_args = [] if params in ("", "void") else [_ctype(p, named=True) for p in params.split(",")]
+        res, args = _lib.SIGNATURES[name]
+        assert res is want_res, f"{name}: returns {ret.strip()}, the table says {res}"
+        assert len(args) == len(want_args), f"{name}: header has {len(want_args)} params"
+        for decl, got, want in zip(params.split(","), args, want_args):
+            assert got is want, f"{name}: parameter '{decl.strip()}' is {want}, the table says {got}"
+        seen += 1
+    assert seen >= 158, f"classified only {seen} prototypes"
+
+
 def test_runtime_options():
     """rs_set_option / rs_get_option: known options round-trip, unknown ones
     and out-of-range values are refused without changing anything."""

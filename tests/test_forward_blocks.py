@@ -722,6 +722,52 @@ def test_outer_and_product_fwd(gpu, F, k):
                     _close("rs_product_fwd", got[:, Wrow - P:], outer64, "outer " + what)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry,dtype,outer", [("rs_embed_inner_fwd", np.int32, False),
+                                               ("rs_embed_inner_fwd", np.int64, False),
+                                               ("rs_embed_product_fwd", np.int32, True),
+                                               ("rs_embed_inner_fwd_hm", np.int32, False)])
+def test_embed_products_from_ids_above_64k_lds(gpu, entry, dtype, outer):
+    """The id path of inner_fast past the 64 KiB default of dynamic LDS, k != 16 (so the _hm entry takes the same
+    branch: no kernarg front end).  48 fields, k = 8: a sample's tile is (384 + 4 + 1128) * 4 = 6,064 B, S = 16,
+    97,024 B; with the outer part 10,576 B, S = 9, 95,184 B.  B = 17: a full workgroup and one of one sample (9
+    and 8 with the outer part).  Vocabularies of 2..4 rows: every row is gathered many times."""
+    st, lb = _lib.stream(), _lib.lib()
+    F, k, B = 48, 8, 17
+    P = F * (F - 1) // 2
+    pairs = 2 * P if outer else P
+    S = _inner_S(F, k, True, pairs)
+    assert (S, S * (F * k + 4 + pairs) * 4) == ((9, 95184) if outer else (16, 97024))
+    rng = np.random.default_rng(4808 + outer)
+    vocab = rng.integers(2, 5, F)
+    table = _nrm(rng, int(vocab.sum()), k) * F32(0.5)
+    ids = _id_case(rng, B, vocab, False)
+    kind = dict(KINDS)[dtype]
+    idd, td, (offd, vocd) = _ids_dev(ids, dtype), _dev(table), _meta(vocab)
+    hoff = np.concatenate([[0], np.cumsum(vocab)[:-1]]).astype(np.int64)
+    hvoc = np.asarray(vocab, np.int64)
+    host = [hoff.ctypes.data, hvoc.ctypes.data] if entry.endswith("_hm") else []
+    W = _nrm(rng, k, P, k) / F32(k)
+    if outer:
+        prep = torch.full((int(lb.rs_outer_prepared_size(F, k)),), float("nan"), dtype=torch.float32, device="cuda")
+        _lib.call("rs_outer_prepare", _dev(W).data_ptr(), F, k, prep.data_ptr(), st)
+    Wrow = F * k + pairs
+
+    def run():
+        flag, y = _flag(), _out(B, Wrow)
+        _lib.call(entry, idd.data_ptr(), kind, F + 2, td.data_ptr(), offd.data_ptr(), vocd.data_ptr(), *host, F, k,
+                  *((1, prep.data_ptr()) if outer else ()), y.data_ptr(), Wrow, B, flag.data_ptr(), st)
+        return flag, y
+
+    flag, y = _twice(run)
+    assert int(flag.item()) == 0, "error flag"
+    got, e = _get(y, Wrow), _gather(table, ids, vocab).astype(F32)
+    assert np.array_equal(got[:, :F * k], e.reshape(B, F * k)), "flat block is not the table rows"
+    _close(entry, got[:, F * k:F * k + P], ref_inner(e), f"inner {np.dtype(dtype).name}")
+    if outer:
+        _close(entry, got[:, F * k + P:], ref_outer(e, W), "outer")
+
+
 # ------------------------------------- pair products and the size-1 softmax
 @pytest.mark.gpu
 @pytest.mark.parametrize("F,k,B", [(2, 1, 3), (3, 5, 7), (26, 16, 5), (2, 16, 1), (26, 1, 2), (3, 16, 4),
