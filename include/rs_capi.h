@@ -722,6 +722,73 @@ int rs_res_tower_bwd(const float* saved, int d, int n_hidden,
                      float* deltas, float* dx0, int64_t dx0_stride,
                      int64_t batch, rs_stream_t stream);
 
+/* ----------------------- multi-gate mixture of experts (MMOE, a18), forward
+ * mmoe_layer.call (layer/interaction.py:479-509) on x [B, d], rows x_stride
+ * apart, with H = hidden, E = n_experts, T = n_tasks:
+ *   expert[b, h, e] = relu(x[b] . expert_matrix[:, h, e] + expert_bias[h, e])
+ *   g_t[b, :]       = softmax(x[b] @ gate_matrix_t + gate_bias_t)   (over E)
+ *   mix_t[b, h]     = sum_e g_t[b, e] * expert[b, h, e]
+ * and, with n_tower_layers >= 1, MMOE.call (model/mmoe.py:24-32): task t's
+ * tower_layer (layer/interaction.py:512-523: Dense(tower_dims[i + 1],
+ * tower_acts[i]) per layer, the last one the linear Dense(output_dim)) on
+ * mix_t — ONE launch over 16-sample tiles; expert outputs, gates, mixes and
+ * tower activations stay in LDS.  The softmax subtracts the row maximum; every
+ * sum has one fixed order (e ascending), a row's result does not depend on the
+ * batch.
+ * tower_dims: host int[n_tower_layers + 1], tower_dims[0] == hidden, the last
+ * = output_dim (may be NULL when n_tower_layers == 0); all towers share the
+ * widths and tower_acts (host int[n_tower_layers]: RS_ACT_NONE, RS_ACT_RELU
+ * or RS_ACT_SIGMOID) but have their own weights.
+ * Caps: d, hidden and every tower width 1..1024; 1 <= E <= 16; 1 <= T <= 8;
+ * roundup((H + T) * E, 16) <= 1024; 0..4 tower layers; and the tile must fit
+ * the LDS: with maxw = max(roundup(d, 16), E * (H | 1) + T * E,
+ * T * roundup(w, 16) over w in {H, tower widths}), 4 * (32 * (roundup(maxw,
+ * 64) + 8) + 4096) <= 160 KiB.  rs_mmoe_ok: 1 when the shape is supported
+ * (that geometry), else 0 — the reference's constructors
+ * (layer/interaction.py:430-436, model/mmoe.py:11-22) take any shape; a
+ * refused one runs as the unfused composition in the host layer.
+ * prepared (rs_mmoe_prepared_size floats, -1 on a bad shape), with dp =
+ * roundup(d, 16), N1p = roundup((H + T) * E, 16), Kp_l / Np_l = roundup(
+ * tower_dims[l] / tower_dims[l + 1], 16):
+ *   dp * N1p + N1p + sum_l T * (Kp_l * Np_l + Np_l)
+ * = [W1 | b1 | layer_0 .. layer_{L-1}]: W1 is ONE matrix [dp, N1p] in MFMA
+ * B-fragment order whose column h * E + e is expert_matrix[:, h, e] (the Keras
+ * tensor [d, H, E] read as [d, H * E]) and column H * E + t * E + e is
+ * gate_matrix_t[:, e]; b1 the biases in the same column order; layer_l = the
+ * T tasks' packed kernels [Kp_l, Np_l] one after another, then their T biases
+ * [Np_l].  Padding is zeros.
+ * rs_mmoe_prepare (mmoe_layer.build :438-477 + the towers' kernels): packs
+ * it.  expert_matrix [d, H, E], expert_bias [H, E] (NULL =
+ * use_expert_bias=False: zeros); gate_matrix / gate_bias: host arrays of T
+ * device pointers ([d, E] / [E]; gate_bias, or any gate_bias[t], NULL =
+ * zeros); tower_W / tower_bias: host arrays of T * n_tower_layers device
+ * pointers, task-major (Keras kernels [in, out]; tower_bias, or any entry,
+ * NULL = zeros).
+ * rs_mmoe_fwd: mix (optional when n_tower_layers >= 1, required when 0 — the
+ * launch is then mmoe_layer.call alone): [B, T * H], rows mix_stride apart,
+ * task t at columns t * H.  y: task t's output [B, output_dim] at y + t *
+ * y_task_stride, rows y_stride apart.  y is bit-identical with and without
+ * mix, and mix with and without the towers.
+ * Stream-ordered, graph-capturable; arguments are validated before any device
+ * work; nothing is launched for batch 0.                                     */
+int rs_mmoe_ok(int d, int hidden, int n_experts, int n_tasks,
+               int n_tower_layers, const int* tower_dims);
+int64_t rs_mmoe_prepared_size(int d, int hidden, int n_experts, int n_tasks,
+                              int n_tower_layers, const int* tower_dims);
+int rs_mmoe_prepare(int d, int hidden, int n_experts, int n_tasks,
+                    const float* expert_matrix, const float* expert_bias,
+                    const float* const* gate_matrix,
+                    const float* const* gate_bias, int n_tower_layers,
+                    const int* tower_dims, const float* const* tower_W,
+                    const float* const* tower_bias, float* prepared,
+                    rs_stream_t stream);
+int rs_mmoe_fwd(const float* x, int64_t x_stride, int d, int hidden,
+                int n_experts, int n_tasks, int n_tower_layers,
+                const int* tower_dims, const int* tower_acts,
+                const float* prepared, float* mix, int64_t mix_stride,
+                float* y, int64_t y_task_stride, int64_t y_stride,
+                int64_t batch, rs_stream_t stream);
+
 /* ------------------------------------------ wide part of Wide&Deep (a17)
  * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
  * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense

@@ -9,8 +9,8 @@ reference's Keras layer / model names and signatures.
 from . import _lib  # noqa: F401
 from .layers import (AFMLayer, Attention, AttentionLayer, BatchNormalization, CrossLayer, Dense, Dice,  # noqa: F401
                      DNNLayer, EmbedLayer, FFMLayer, FGCNNLayer, FMLayer, InnerProductLayer, InteractionLayer,
-                     OuterProductLayer, ResLayer, WideLayer, sigmoid_combine)
-from .models import AFM, DCN, DIN, FFM, FM, NFM, PNN, DeepCrossing, DeepFM, WideDeep  # noqa: F401
+                     OuterProductLayer, ResLayer, WideLayer, mmoe_layer, sigmoid_combine, tower_layer)
+from .models import AFM, DCN, DIN, FFM, FM, MMOE, NFM, PNN, DeepCrossing, DeepFM, WideDeep  # noqa: F401
 from .dataset import create_criteo_dataset, denseFeature, features_dict, sparseFeature  # noqa: F401
 
 __version__ = "0.1.0"

@@ -99,6 +99,10 @@ SIGNATURES = {
     "rs_res_tower_bwd_prepared_size": (L, [I, I, P, I]),
     "rs_res_tower_prepare_bwd": (I, [I, I, P, I, P, P, P, P]),
     "rs_res_tower_bwd": (I, [P, I, I, P, I, P, P, L, P, P, P, L, L, P]),
+    "rs_mmoe_ok": (I, [I, I, I, I, I, P]),
+    "rs_mmoe_prepared_size": (L, [I, I, I, I, I, P]),
+    "rs_mmoe_prepare": (I, [I, I, I, I, P, P, P, P, I, P, P, P, P, P]),
+    "rs_mmoe_fwd": (I, [P, L, I, I, I, I, I, P, P, P, P, L, P, L, L, L, P]),
     "rs_wide_onehot_fwd":(I, [P, I, L, P, L, I, P, P, I, P, P, P, L, P, P]),
     "rs_concat_pieces": (I, [I, P, P, P, P, P, P, P, P, L, L, P, P]),
     "rs_deepfm_fused_ok": (I, [I, I, I, I, I, P]),

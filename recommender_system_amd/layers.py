@@ -15,6 +15,10 @@ Each class keeps the reference layer's name, constructor arguments and
   Dice(axis=-1, epsilon=1e-9)                 layer/interaction.py:410-425
   ResLayer(hidden_units)                      layer/interaction.py:261-278
   WideLayer()                                 layer/interaction.py:11-26
+  mmoe_layer(hidden_units, num_experts, num_tasks, use_expert_bias,
+             use_gate_bias)                   layer/interaction.py:429-509
+  tower_layer(hidden_units, output_dim, activation='relu')
+                                              layer/interaction.py:512-523
   Dense / PReLU / BatchNormalization          the Keras layers the models use
 
 Weights are built lazily on the first call from the input shape, like Keras
@@ -1293,6 +1297,184 @@ class ResLayer(KerasModule):
         call("rs_res_tower_fwd", ptr(x), x.stride(0), d, nh, (C.c_int * nh)(*self.hidden_units), 1,
              ptr(self.prepared()), 0, ptr(out), out.stride(0), B, _stream())
         return out
+
+
+_MMOE_MAXL = 4  # mmoe.hip MMOE_MAXL (tower layers, the output Dense included)
+
+
+def _mmoe_dims(hidden, towers):
+    """tower_dims of the rs_mmoe_* entries: [H] alone for the layer-only form."""
+    return [int(hidden)] + ([l.units for l in towers[0]._layers()] if towers else [])
+
+
+def _mmoe_ok(d, hidden, n_experts, n_tasks, dims):
+    return bool(_lib.lib().rs_mmoe_ok(int(d), int(hidden), int(n_experts), int(n_tasks), len(dims) - 1,
+                                      (C.c_int * len(dims))(*dims)))
+
+
+def _mmoe_params(layer, towers):
+    ps = [layer.expert_matrix, layer.expert_bias] + layer.gate_matrix + (layer.gate_bias or [])
+    ps += [p for tw in towers for l in tw._layers() for p in (l.kernel, l.bias)]
+    return [p for p in ps if p is not None]
+
+
+def _mmoe_prepare(layer, towers, device):
+    """The packed image (rs_mmoe_prepare) of a built mmoe_layer, alone or with
+    one tower_layer per task (equal widths)."""
+    d, H, E, T = layer.input_dim, layer.hidden_units, layer.num_experts, layer.num_tasks
+    dims = _mmoe_dims(H, towers)
+    L = len(dims) - 1
+    ci = (C.c_int * len(dims))(*dims)
+    size = _lib.lib().rs_mmoe_prepared_size(d, H, E, T, L, ci)
+    if size < 0:
+        _lib.check(-1, "rs_mmoe_prepared_size")
+    pa = lambda ts: (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
+    tl = [l for tw in towers for l in tw._layers()]
+    prep = torch.empty(size, dtype=torch.float32, device=device)
+    call("rs_mmoe_prepare", d, H, E, T, ptr(layer.expert_matrix), ptr(layer.expert_bias), pa(layer.gate_matrix),
+         pa(layer.gate_bias) if layer.gate_bias else None, L, ci, pa([l.kernel for l in tl]) if tl else None,
+         pa([l.bias for l in tl]) if tl else None, ptr(prep), _stream())
+    return prep
+
+
+def _mmoe_input(inputs, layer):
+    """The float32 input rows [B, d] (contiguous columns) of a built-on-demand
+    mmoe_layer."""
+    x = inputs if (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32) \
+        else _to_device_f32(inputs, layer._dev)
+    if x.dim() != 2:
+        raise ValueError(f"mmoe_layer: expected a [batch, features] matrix, got shape {tuple(x.shape)}")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    if not layer.built:
+        layer.build(x.shape[-1])
+    if x.shape[1] != layer.input_dim:
+        raise ValueError(f"mmoe_layer built for {layer.input_dim} inputs, got {x.shape[1]}")
+    return x
+
+
+class mmoe_layer(KerasModule):
+    """mmoe_layer(hidden_units, num_experts, num_tasks, use_expert_bias=True,
+    use_gate_bias=True) — layer/interaction.py:429-509: num_experts experts
+    relu(x @ expert_matrix[:, :, e] + expert_bias[:, e]), per task a gate
+    softmax(x @ gate_matrix{t} + gate_bias{t}) over the experts, and the gated
+    sum: ``forward(x[B, d])`` returns num_tasks tensors [B, hidden_units], views
+    of one [B, num_tasks * hidden_units] buffer.
+
+    Weights (built from the input width on the first call or by ``build(d)``),
+    all random_normal N(0, 0.05) as in the reference: ``expert_matrix``
+    [d, H, E], ``expert_bias`` [H, E], ``gate_matrix{t}`` [d, E],
+    ``gate_bias{t}`` [E].
+
+    The forward is ONE rs_mmoe_fwd launch without towers (mmoe.hip) when
+    ``fused_ok()``; otherwise ``forward_unfused``: rs_dense_fwd for the
+    experts, one per gate, torch softmax / multiply / sum."""
+
+    def __init__(self, hidden_units, num_experts, num_tasks, use_expert_bias=True, use_gate_bias=True, device=None,
+                 seed=None, input_dim=None):
+        super().__init__(device, seed)
+        self.hidden_units, self.num_experts, self.num_tasks = int(hidden_units), int(num_experts), int(num_tasks)
+        if min(self.hidden_units, self.num_experts, self.num_tasks) < 1:
+            raise ValueError("mmoe_layer: hidden_units, num_experts and num_tasks must be >= 1")
+        self.use_expert_bias, self.use_gate_bias = bool(use_expert_bias), bool(use_gate_bias)
+        self.expert_matrix = self.expert_bias = None
+        self.input_dim = None
+        if input_dim is not None:
+            self.build(input_dim)
+
+    @property
+    def built(self):
+        return self.expert_matrix is not None
+
+    def build(self, d):
+        d, H, E = int(d), self.hidden_units, self.num_experts
+        new = lambda *shape: nn.Parameter(_normal(shape, self._gen, self._dev), requires_grad=False)
+        self.expert_matrix = new(d, H, E)
+        if self.use_expert_bias:
+            self.expert_bias = new(H, E)
+        for t in range(self.num_tasks):
+            setattr(self, f"gate_matrix{t}", new(d, E))
+        if self.use_gate_bias:
+            for t in range(self.num_tasks):
+                setattr(self, f"gate_bias{t}", new(E))
+        self.input_dim = d
+        self._invalidate()
+
+    @property
+    def gate_matrix(self):
+        return [getattr(self, f"gate_matrix{t}") for t in range(self.num_tasks)]
+
+    @property
+    def gate_bias(self):
+        return [getattr(self, f"gate_bias{t}") for t in range(self.num_tasks)] if self.use_gate_bias else None
+
+    def keras_weights(self):
+        if not self.built:
+            raise RuntimeError("mmoe_layer: not built (call build(d) or run a forward first)")
+        return super().keras_weights()
+
+    def _invalidate(self):
+        self.__dict__.pop("_mmoe_prep", None)
+
+    def fused_ok(self):
+        H = self.hidden_units
+        return self.built and _mmoe_ok(self.input_dim, H, self.num_experts, self.num_tasks, [H])
+
+    def prepared(self):
+        """Weights packed for rs_mmoe_fwd without towers, cached until a weight changes."""
+        key = tuple((p._version, p.data_ptr()) for p in _mmoe_params(self, []))
+        ent = self.__dict__.get("_mmoe_prep")
+        if ent is None or ent[0] != key:
+            ent = self.__dict__["_mmoe_prep"] = (key, _mmoe_prepare(self, [], self._dev))
+        return ent[1]
+
+    def forward_fused(self, x):
+        """mmoe_layer.call as one launch: the mixes [B, T * H]."""
+        B, d = x.shape
+        H, E, T = self.hidden_units, self.num_experts, self.num_tasks
+        mix = torch.empty(B, T * H, dtype=torch.float32, device=self._dev)
+        call("rs_mmoe_fwd", ptr(x), x.stride(0), d, H, E, T, 0, (C.c_int * 1)(H), None, ptr(self.prepared()), ptr(mix),
+             mix.stride(0), None, 0, 0, B, _stream())
+        return mix
+
+    def forward_unfused(self, x):
+        """The composition from the older entries: the mixes [B, T * H]."""
+        B, d = x.shape
+        H, E, T = self.hidden_units, self.num_experts, self.num_tasks
+        mix = torch.empty(B, T * H, dtype=torch.float32, device=self._dev)
+        if B == 0:
+            return mix
+        experts = torch.empty(B, H * E, dtype=torch.float32, device=self._dev)
+        call("rs_dense_fwd", ptr(x), x.stride(0), ptr(self.expert_matrix), ptr(self.expert_bias), None,
+             _lib.ACT["relu"], ptr(experts), experts.stride(0), B, d, H * E, _stream())
+        experts = experts.view(B, H, E)
+        gb = self.gate_bias
+        for t, gm in enumerate(self.gate_matrix):
+            logits = torch.empty(B, E, dtype=torch.float32, device=self._dev)
+            call("rs_dense_fwd", ptr(x), x.stride(0), ptr(gm), ptr(gb[t]) if gb else None, None, 0, ptr(logits),
+                 logits.stride(0), B, d, E, _stream())
+            gate = torch.softmax(logits, dim=-1)
+            mix[:, t * H:(t + 1) * H] = (experts * gate.unsqueeze(1)).sum(-1)
+        return mix
+
+    def forward(self, inputs):
+        x = _mmoe_input(inputs, self)
+        mix = self.forward_fused(x) if self.fused_ok() else self.forward_unfused(x)
+        H = self.hidden_units
+        return [mix[:, t * H:(t + 1) * H] for t in range(self.num_tasks)]
+
+
+class tower_layer(DNNLayer):
+    """tower_layer(hidden_units, output_dim, activation='relu') —
+    layer/interaction.py:512-523: DNNLayer without the Dropout (same weight
+    names, dense_{i}/… and dense_out/…).  (The reference's __init__ assigns its
+    sub-layers before super().__init__(), the reverse of the order Keras asks
+    for; recorded in DESIGN.md, not imitated and not "fixed" there.)"""
+
+    def __init__(self, hidden_units, output_dim, activation="relu", device=None, seed=None, input_dim=None):
+        super().__init__(hidden_units, output_dim, activation, dropout=0.0, device=device, seed=seed)
+        if input_dim is not None:
+            self.build(input_dim)
 
 
 class WideLayer(KerasModule):

@@ -19,6 +19,8 @@ models (Hcyand/recommender_system, algorithm/deep_learning/model/):
   FFM(feature_columns, k, w_reg=1e-4, v_reg=1e-4)                 model/ffm.py:10-22
   DeepCrossing(feature_columns, k, hidden_units, res_layer_num)   model/deepCrossing.py:15-32
   WideDeep(feature_columns, hidden_units, output_dim, activation) model/wideDeep.py:14-34
+  MMOE(mmoe_hidden_units, num_experts, num_tasks, tower_hidden_units, output_dim,
+       activation='relu', use_expert_bias=True, use_gate_bias=True) model/mmoe.py:10-32
 
 Criteo-style models take the reference's packed input X[B, 13+F] (dense
 features followed by label-encoded sparse ids, as floats — Keras casts them to
@@ -48,7 +50,8 @@ from ._lib import call, ptr
 from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense, DNNLayer, EmbedLayer, FFMLayer,
                      FGCNNLayer, FMLayer, InnerProductLayer, OuterProductLayer,
                      KerasModule, ResLayer, TowerMixin, WideLayer, sigmoid_combine, _ids_tensor, _to_device_f32,
-                     _ErrFlag, _RES_MAXH, _RES_MAXU, _res_key, _res_ok, _res_prepare)
+                     _ErrFlag, _RES_MAXH, _RES_MAXU, _res_key, _res_ok, _res_prepare, mmoe_layer, tower_layer,
+                     _MMOE_MAXL, _mmoe_dims, _mmoe_input, _mmoe_ok, _mmoe_params, _mmoe_prepare)
 
 
 def _split_criteo(inputs, nd, device):
@@ -1877,3 +1880,105 @@ class WideDeep(KerasModule):
             return ups
 
         return self._train(wide, wide_update, ids, labels, lr, return_loss, check_ids, dropout)
+
+
+_MMOE_ACTS = ("relu", "sigmoid", "linear", None)  # what rs_mmoe_fwd's towers take (tower_layer's Dense has no alpha)
+
+
+class MMOE(KerasModule):
+    """MMOE(mmoe_hidden_units, num_experts, num_tasks, tower_hidden_units,
+    output_dim, activation='relu', use_expert_bias=True, use_gate_bias=True) —
+    model/mmoe.py:10-32: a float matrix x [B, d] through mmoe_layer, then task
+    t's tower_layer on task t's mix; returns num_tasks tensors [B, output_dim].
+    Forward only, as the reference (it has no loss or fit loop for MMOE).
+
+    The mmoe_layer builds from the input width on the first call (or
+    ``input_dim``); the towers are built at construction (their input is
+    mmoe_hidden_units).
+
+    ``forward_fused`` is ONE launch (rs_mmoe_fwd: experts, gates, mixes and
+    tower activations stay in LDS); ``forward_unfused`` is the composition from
+    the older entries (rs_dense_fwd for the experts and per gate, torch softmax
+    / multiply / sum, one rs_mlp_fwd per tower).  ``forward`` takes the fused
+    path when ``fused_ok()``."""
+
+    def __init__(self, mmoe_hidden_units, num_experts, num_tasks, tower_hidden_units, output_dim, activation="relu",
+                 use_expert_bias=True, use_gate_bias=True, device=None, seed=None, input_dim=None):
+        super().__init__(device, seed)
+        self.activation = activation
+        self.output_dim = int(output_dim)
+        self.mmoe_layer = mmoe_layer(mmoe_hidden_units, num_experts, num_tasks, use_expert_bias, use_gate_bias,
+                                     device=device, seed=_subseed(self._gen), input_dim=input_dim)
+        self.tower_layer = torch.nn.ModuleList(
+            [tower_layer(tower_hidden_units, output_dim, activation, device=device, seed=_subseed(self._gen),
+                         input_dim=self.mmoe_layer.hidden_units) for _ in range(self.mmoe_layer.num_tasks)])
+
+    def build(self, d):
+        self.mmoe_layer.build(d)
+        self._invalidate()
+
+    def keras_weights(self):
+        out = _prefixed("mmoe_layer", self.mmoe_layer.keras_weights())
+        for t, tower in enumerate(self.tower_layer):
+            out.update(_prefixed(f"tower_layer_{t}", tower.keras_weights()))
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        if strict:
+            unknown = set(weights) - set(self.keras_weights())
+            if unknown:
+                raise KeyError(f"unknown weights {sorted(unknown)}")
+        _set_prefixed(self.mmoe_layer, "mmoe_layer", weights, strict)
+        for t, tower in enumerate(self.tower_layer):
+            _set_prefixed(tower, f"tower_layer_{t}", weights, strict)
+        self._weights_changed()
+
+    def _invalidate(self):
+        self.__dict__.pop("_mmoe_prep", None)
+
+    def _dims(self):
+        return _mmoe_dims(self.mmoe_layer.hidden_units, list(self.tower_layer))
+
+    def fused_ok(self):
+        m = self.mmoe_layer
+        dims = self._dims()
+        return (m.built and self.activation in _MMOE_ACTS and len(dims) - 1 <= _MMOE_MAXL
+                and _mmoe_ok(m.input_dim, m.hidden_units, m.num_experts, m.num_tasks, dims))
+
+    def prepared(self):
+        """The layer's and every tower's weights packed for rs_mmoe_fwd,
+        cached until a weight changes."""
+        towers = list(self.tower_layer)
+        key = tuple((p._version, p.data_ptr()) for p in _mmoe_params(self.mmoe_layer, towers))
+        ent = self.__dict__.get("_mmoe_prep")
+        if ent is None or ent[0] != key:
+            ent = self.__dict__["_mmoe_prep"] = (key, _mmoe_prepare(self.mmoe_layer, towers, self._dev))
+        return ent[1]
+
+    def forward_fused(self, inputs, mix=None):
+        """MMOE.call as ONE kernel.  mix (optional, [B, T * H]) receives the
+        mmoe_layer's outputs, task t at columns t * H."""
+        m = self.mmoe_layer
+        x = _mmoe_input(inputs, m)
+        B, d = x.shape
+        dims = self._dims()
+        n = len(dims) - 1
+        acts = [_lib.ACT[self.activation]] * (n - 1) + [0]
+        y = torch.empty(m.num_tasks, B, self.output_dim, dtype=torch.float32, device=self._dev)
+        call("rs_mmoe_fwd", ptr(x), x.stride(0), d, m.hidden_units, m.num_experts, m.num_tasks, n,
+             (C.c_int * (n + 1))(*dims), (C.c_int * n)(*acts), ptr(self.prepared()), ptr(mix),
+             0 if mix is None else mix.stride(0), ptr(y), y.stride(0), y.stride(1), B, _lib.stream())
+        return [y[t] for t in range(m.num_tasks)]
+
+    def forward_unfused(self, inputs):
+        """mmoe_layer.forward_unfused, then one DNNLayer forward per tower."""
+        m = self.mmoe_layer
+        mix = m.forward_unfused(_mmoe_input(inputs, m))
+        H = m.hidden_units
+        return [tower(mix[:, t * H:(t + 1) * H]) for t, tower in enumerate(self.tower_layer)]
+
+    def forward(self, inputs):
+        x = _mmoe_input(inputs, self.mmoe_layer)  # (builds the layer: fused_ok needs its width)
+        if self.fused_ok():
+            return self.forward_fused(x)
+        return self.forward_unfused(x)
