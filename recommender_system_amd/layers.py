@@ -45,6 +45,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import call, ptr
+from ._train_ops import _subseed, scratch
 
 _DEFAULT_DEVICE = "cuda"
 
@@ -966,9 +967,7 @@ class Attention(KerasModule):
             wsz = _lib.lib().rs_din_attention_gen_workspace_size(B, T, k, n, hid)
             if wsz < 0:
                 _lib.check(-1, "rs_din_attention_gen_workspace_size")
-            ws = self.__dict__.get("_gen_ws")
-            if ws is None or ws.numel() < wsz:
-                ws = self.__dict__["_gen_ws"] = torch.empty(wsz, dtype=torch.uint8, device=self._dev)
+            ws = scratch(self, "_gen_ws", wsz)
             pa = lambda ts: (C.c_void_p * max(n, 1))(*[ptr(t) for t in ts])
             call("rs_din_attention_gen_fwd", ptr(q), ptr(key), ptr(value), ptr(mask), T, k, n, hid, pa(self.kernels), pa(self.biases), pa(self.alphas),
                  ptr(self.out_kernel), ptr(self.out_bias), ptr(out), B, ptr(ws), ws.numel(), s)
@@ -1056,10 +1055,6 @@ class AttentionLayer(KerasModule):
             out = torch.empty(B, k, dtype=torch.float32, device=self._dev)
         call("rs_attention_pool_fwd", ptr(x), P * k, P, k, B, ptr(out), _stream())
         return out
-
-
-def _subseed(gen):
-    return int(torch.randint(0, 2 ** 31, (1,), generator=gen))
 
 
 _AFM_MODES = {"att": 0, "avg": 1, "max": 2}

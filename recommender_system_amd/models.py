@@ -54,166 +54,10 @@ from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense,
                      _MMOE_MAXL, _mmoe_dims, _mmoe_input, _mmoe_ok, _mmoe_params, _mmoe_prepare)
 
 
-def _split_criteo(inputs, nd, device):
-    """(dense f32 [B,nd], ids [B,F]) from X[B,nd+F] or a (dense, ids) pair."""
-    if isinstance(inputs, (tuple, list)):
-        dense, ids = inputs
-        return _to_device_f32(dense, device), _ids_tensor(ids, device)
-    X = _to_device_f32(inputs, device)  # Keras autocast (float64 -> float32)
-    return X[:, :nd], X[:, nd:]
-
-
-def _subseed(gen):
-    return int(torch.randint(0, 2 ** 31, (1,), generator=gen))
-
-
-def _dnn_backward(layers, acts, delta, gw, emp, st, outs=None, drop=None):
-    """Backward through Dense layers (relu or linear hidden activations):
-    delta = dL/d(pre-activation) of the top layer; returns the (layer, dW, db)
-    gradients and dL/d(acts[0]).  dW = a_in^T delta (split-K rs_gemm), db =
-    column sums, delta_below = (delta W^T) [a_in > 0] (mask epilogue).
-    outs: optional [(dW, db)] per layer to write into (contiguous views).
-    drop: (_Dropout, rate, offsets) of the forward's hidden-layer dropout
-    draws — delta_below is multiplied by the same keep / (1 - rate)."""
-    B = acts[0].shape[0]
-    grads = []
-    for li in reversed(range(len(layers))):
-        L, a_in = layers[li], acts[li]
-        K_in, N_out = L.kernel.shape
-        dW, db = outs[li] if outs is not None else (emp(K_in, N_out), emp(N_out))
-        call("rs_gemm", 1, 0, K_in, N_out, B, 1.0, ptr(a_in), a_in.stride(0), ptr(delta), delta.stride(0), 0.0,
-             ptr(dW), N_out, None, 0, *gw, st)
-        call("rs_col_sum", ptr(delta), delta.stride(0), B, N_out, ptr(db), st)
-        grads.append((L, dW, db))
-        relu_below = li > 0 and layers[li - 1].activation == "relu"
-        prev = emp(B, K_in)
-        call("rs_gemm", 0, 1, B, K_in, N_out, 1.0, ptr(delta), delta.stride(0), ptr(L.kernel), N_out, 0.0,
-             ptr(prev), K_in, ptr(a_in) if relu_below else None, a_in.stride(0), *gw, st)
-        if drop is not None and 0 < li <= len(drop[2]):  # acts[li] is dropped hidden output li-1
-            rng, rate, offs = drop
-            rng.redraw(prev, rate, offs[li - 1], st)
-        delta = prev
-    if drop is not None:
-        drop[0].end_step(st)
-    return grads, delta
-
-
-def _dnn_updates(grads, l2=0.0):
-    """[(w, grad, n, l2)] of Dense layers' kernels and biases (for
-    _lib.sgd_update_multi)."""
-    out = []
-    for L, dW, db in grads:
-        out.extend([(L.kernel, dW, dW.numel(), l2), (L.bias, db, db.numel(), l2)])
-    return out
-
-
-def _dnn_apply(grads, lr, st, l2=0.0):
-    _lib.sgd_update_multi(_dnn_updates(grads, l2), lr, st)
-
-
-def _embedding_sgd(model, ids, dx, ldx, lr, st):
-    """Row-sparse SGD of the looked-up rows from dL/dx's embedding block
-    (columns nd.., row stride ldx): rs_embedding_sgd, duplicates summed in
-    lookup order."""
-    e = model.embed_layer
-    B = ids.shape[0]
-    ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * e.n_fields)
-    ws = model.__dict__.get("_emb_ws")
-    if ws is None or ws.numel() < ws_n:
-        ws = model.__dict__["_emb_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=model._dev)
-    call("rs_embedding_sgd", ptr(e.table), e.total_rows, e.k, ptr(ids), _lib.id_kind(ids), ids.stride(0),
-         ptr(e.field_offsets), ptr(e.field_vocab), e.n_fields, B, ptr(dx) + 4 * model.nd, ldx, float(lr), ptr(ws),
-         None, st)
-
-
-def _check_train_tower(name, dnn):
-    if any(l.activation not in (None, "linear", "relu") for l in dnn.hidden_layer):
-        raise NotImplementedError(f"{name}.train_step: 'relu' or linear hidden layers only")
-
-
-class _Dropout:
-    """DNNLayer's Dropout(rate) in training steps (layer/interaction.py:35,44;
-    active under compile_fit's model.fit, utils/compile_fit.py:14): inverted
-    dropout with counter-based masks (rs_dropout_at: Philox4x32-10, key =
-    seed, one counter per 4 elements).  Every draw of a step takes the next
-    offset range relative to a counter in DEVICE memory, the backward
-    regenerates a draw's mask from the same (seed, counter + rel) instead of
-    storing it, and end_step() advances the counter on the stream by the
-    step's total — so a captured hipGraph of a training step draws fresh
-    masks on every replay.  TF's own draws cannot be reproduced;
-    oracle.dropout_multiplier restates this generator."""
-
-    def __init__(self, seed, device=None):
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.base = torch.zeros(1, dtype=torch.int64, device=device if device is not None else "cuda")
-        self.rel = 0
-
-    @property
-    def offset(self):
-        """The absolute offset the next draw takes (reads the device counter)."""
-        return int(self.base.item()) + self.rel
-
-    def draw(self, t, rate, st):
-        """Apply a fresh mask to t [rows, cols] in place; returns its offset
-        relative to the step's counter."""
-        off = self.rel
-        self.redraw(t, rate, off, st)
-        self.rel += (t.shape[0] * t.shape[1] + 3) // 4 * 4
-        return off
-
-    def take(self, n):
-        """Reserve the next n elements' range (a draw made elsewhere)."""
-        off = self.rel
-        self.rel += (int(n) + 3) // 4 * 4
-        return off
-
-    def redraw(self, t, rate, rel, st):
-        call("rs_dropout_at", ptr(t), t.stride(0), t.shape[0], t.shape[1], float(rate), self.seed, ptr(self.base),
-             int(rel), st)
-
-    def end_step(self, st):
-        """Advance the device counter past this step's draws."""
-        if self.rel:
-            call("rs_dropout_advance", ptr(self.base), int(self.rel), st)
-            self.rel = 0
-
-
-def _dropout_rate(dnn, dropout):
-    """The rate a training step applies: DNNLayer's own (Keras' fit runs the
-    Dropout layers in training mode) unless dropout=False turns it off, or a
-    float overrides it."""
-    if dropout is False:
-        return 0.0
-    if dropout is None or dropout is True:
-        return float(getattr(dnn, "dropout", 0) or 0)
-    return float(dropout)
-
-
-def _dropout_rng(model):
-    rng = model.__dict__.get("_drop_rng")
-    if rng is None:
-        rng = model.__dict__["_drop_rng"] = _Dropout(_subseed(model._gen) * 2654435761 + 97, model._dev)
-    return rng
-
-
-def _dnn_train_forward(model, dnn, x, rate, st):
-    """Hidden layers of DNNLayer in training: Dense + activation, then the
-    dropout draw (rate > 0).  Returns (acts, drop) for _dnn_backward."""
-    acts, offs = [x], []
-    rng = _dropout_rng(model) if rate > 0 else None
-    for layer in dnn.hidden_layer:
-        a = layer(acts[-1])
-        if rng is not None:
-            offs.append(rng.draw(a, rate, st))
-        acts.append(a)
-    return acts, ((rng, rate, offs) if rng is not None else None)
-
-
-def _gemm_ws(model, nbytes):
-    ws = model.__dict__.get("_gemm_wsbuf")
-    if ws is None or ws.numel() < max(nbytes, 1):
-        ws = model.__dict__["_gemm_wsbuf"] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=model._dev)
-    return ws
+from ._train_ops import (_Dropout, _check_train_tower, _dnn_apply, _dnn_backward, _dnn_train_forward,  # noqa: F401
+                         _dnn_updates, _dropout_rate, _dropout_rng, _split_criteo, _subseed, bce_head,
+                         bce_head_logit, bn_train_bwd, bn_train_fwd, dense_backward, embedding_sgd,
+                         embedding_sgd_strided, fm_backward, fm_xv, gemm_need, gemm_ws, scratch)
 
 
 class FM(KerasModule):
@@ -271,10 +115,7 @@ class FM(KerasModule):
         if not fm.built:  # (a host sum: not inside a graph capture)
             fm.build(nd + int(voc.sum()))
         n = fm.w1.shape[0]
-        ws_n = _lib.lib().rs_fm_train_workspace_size(B, F, fm.k, nd)
-        ws = self.__dict__.get("_train_ws")
-        if ws is None or ws.numel() < ws_n:
-            ws = self.__dict__["_train_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=self._dev)
+        ws = scratch(self, "_train_ws", _lib.lib().rs_fm_train_workspace_size(B, F, fm.k, nd))
         loss = torch.empty(B, dtype=torch.float32, device=self._dev) if return_loss else None
         err = _ErrFlag(self._dev)
         call("rs_fm_train_step", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense), dense.stride(0), nd,
@@ -372,28 +213,18 @@ class DeepFM(KerasModule):
         acts, drop = _dnn_train_forward(self, dnn, x, rate, st)
         dnn_out = dnn.output_layer(acts[-1])
         fm_out = fm(x)
-        s = emp(B, kfm)
-        gws = self._gemm_ws(max(_lib.lib().rs_gemm_workspace_size(L.kernel.shape[0], L.kernel.shape[1], B)
-                                for L in layers))
-        gw = (ptr(gws), gws.numel())
-        call("rs_gemm", 0, 0, B, kfm, d, 1.0, ptr(x), d, ptr(fm.v), kfm, 0.0, ptr(s), kfm, None, 0, *gw, st)
-        g_fm, g_dnn = emp(B), emp(B)
-        loss = emp(B) if return_loss else None
-        call("rs_head_grad", ptr(fm_out), ptr(dnn_out), ptr(labels), B, 0.5, 0.5, ptr(g_fm), ptr(g_dnn), ptr(loss), st)
+        gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in layers]))
+        s = fm_xv(x, fm.v, gw, st)
+        g_fm, g_dnn, loss = bce_head(fm_out, dnn_out, labels, 0.5, 0.5, return_loss, st)
         grads, delta = _dnn_backward(layers, acts, g_dnn.view(B, 1), gw, emp, st, drop=drop)
         dx = delta  # [B, d]: the DNN's gradient w.r.t. x; the FM's is added next
-        call("rs_fm_x_grad", ptr(x), d, ptr(s), ptr(fm.w1), ptr(fm.v), B, d, kfm, ptr(g_fm), ptr(dx), d, st)
-        dw1, dv, dw0 = emp(d), emp(d, kfm), emp(1)
-        call("rs_fm_param_grads", ptr(x), d, ptr(s), ptr(fm.v), B, d, kfm, ptr(g_fm), ptr(dw1), ptr(dv), ptr(dw0), st)
+        dw1, dv, dw0 = fm_backward(x, s, fm.w1, fm.v, g_fm, dx, st)
         # updates (every gradient above used the pre-step weights)
         _lib.sgd_update_multi(_dnn_updates(grads) + [(fm.w1, dw1, d, fm.reg_w), (fm.v, dv, d * kfm, fm.reg_b),
                                                      (fm.w0, dw0, 1, 0.0)], lr, st)
-        _embedding_sgd(self, ids, dx, d, lr, st)
+        embedding_sgd(e, ids, ptr(dx) + 4 * self.nd, d, lr, st, self)
         self._weights_changed()  # packed operand images of the old weights are stale
         return loss
-
-    def _gemm_ws(self, nbytes):
-        return _gemm_ws(self, nbytes)
 
     def _fused_rows(self):
         """Tower input permutation for the fused kernel: its LDS tile holds
@@ -515,9 +346,7 @@ class DCN(KerasModule):
         dz_n = d + od
         emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         layers = list(dnn.hidden_layer) + [dnn.output_layer]
-        gws = _gemm_ws(self, max(_lib.lib().rs_gemm_workspace_size(K, N, B)
-                                 for K, N in [L.kernel.shape for L in layers] + [(d, 1), (dz_n, 1)]))
-        gw = (ptr(gws), gws.numel())
+        gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in layers] + [(d, 1, B), (dz_n, 1, B)]))
         # forward, keeping what the backward needs
         x = e.gather(ids, dense, check_ids=check_ids)
         zc = emp(B, dz_n)  # [cross_out | dnn_out], the output Dense's input
@@ -532,14 +361,9 @@ class DCN(KerasModule):
         dnn.output_layer(acts[-1], out=zc[:, d:])
         logit = emp(B)
         call("rs_dense_fwd", ptr(zc), dz_n, ptr(out.kernel), ptr(out.bias), None, 0, ptr(logit), 1, B, dz_n, 1, st)
-        g, g0 = emp(B), emp(B)
-        loss = emp(B) if return_loss else None
-        call("rs_head_grad", ptr(logit), ptr(logit), ptr(labels), B, 1.0, 0.0, ptr(g), ptr(g0), ptr(loss), st)
+        g, loss = bce_head_logit(logit, labels, return_loss, st)
         # output Dense: dWo = zc^T g, dbo = sum g, dzc = g Wo^T
-        dWo, dbo, dzc = emp(dz_n, 1), emp(1), emp(B, dz_n)
-        call("rs_gemm", 1, 0, dz_n, 1, B, 1.0, ptr(zc), dz_n, ptr(g), 1, 0.0, ptr(dWo), 1, None, 0, *gw, st)
-        call("rs_col_sum", ptr(g), 1, B, 1, ptr(dbo), st)
-        call("rs_gemm", 0, 1, B, dz_n, 1, 1.0, ptr(g), 1, ptr(out.kernel), 1, 0.0, ptr(dzc), dz_n, None, 0, *gw, st)
+        dWo, dbo, dzc = dense_backward(out.kernel, zc, g.view(B, 1), gw, emp, st)
         # DNN backward from dzc[:, d:], then the CrossNet's from dzc[:, :d]
         grads, dx = _dnn_backward(layers, acts, dzc[:, d:], gw, emp, st, drop=drop)
         if Lc:
@@ -558,7 +382,7 @@ class DCN(KerasModule):
         for l in range(Lc):
             upd += [(cl.cross_weight[l], dWc[l], d, cl.reg_w), (cl.cross_bias[l], dBc[l], d, cl.reg_b)]
         _lib.sgd_update_multi(upd, lr, st)
-        _embedding_sgd(self, ids, dx, d, lr, st)
+        embedding_sgd(e, ids, ptr(dx) + 4 * self.nd, d, lr, st, self)
         self.__dict__["_keep"] = (W, Bc)  # stream-ordered lifetime of the stacked operands
         self._weights_changed()
         return loss
@@ -769,16 +593,13 @@ class PNN(KerasModule):
         emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self._dev)
         x = self.product_inputs(inputs, check_ids)  # [B, F*k + P]: [flat | inner]
         layers = list(dnn.hidden_layer) + [dnn.output_layer]
-        acts = [x]
-        for layer in dnn.hidden_layer:
-            acts.append(layer(acts[-1]))
+        acts, _ = _dnn_train_forward(self, dnn, x, 0.0, st)  # (rate 0: no draw, as the loop)
         pre = dnn.output_layer(acts[-1])
         g = emp(B)
         loss = emp(B) if return_loss else None
         call("rs_bce_prob_grad", ptr(pre), pre.stride(0), ptr(labels), B, ptr(g), ptr(loss), st)
-        gws = _gemm_ws(self, max(_lib.lib().rs_gemm_workspace_size(L.kernel.shape[0], L.kernel.shape[1], B)
-                                 for L in layers))
-        grads, delta = _dnn_backward(layers, acts, g.view(B, 1), (ptr(gws), gws.numel()), emp, st)
+        gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in layers]))
+        grads, delta = _dnn_backward(layers, acts, g.view(B, 1), gw, emp, st)
         w = self.width
         P = F * (F - 1) // 2
         de = emp(B, F * k)
@@ -798,12 +619,7 @@ class PNN(KerasModule):
         if dW is not None:
             upd.append((self.outer_product_layer.W, dW, dW.numel(), 0.0))
         _lib.sgd_update_multi(upd, lr, st)
-        ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * F)
-        ws = self.__dict__.get("_emb_ws")
-        if ws is None or ws.numel() < ws_n:
-            ws = self.__dict__["_emb_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=self._dev)
-        call("rs_embedding_sgd", ptr(e.table), e.total_rows, k, ptr(ids), _lib.id_kind(ids), ids.stride(0),
-             ptr(e.field_offsets), ptr(e.field_vocab), F, B, ptr(de), F * k, float(lr), ptr(ws), None, st)
+        embedding_sgd(e, ids, ptr(de), F * k, lr, st, self)
         self._weights_changed()
         return loss
 
@@ -1068,8 +884,8 @@ class DIN(TowerMixin, KerasModule):
         lb = _lib.lib()
         # one scratch buffer for every stream-ordered call below (gemm split-K
         # slices, column-sum slices, the PReLU backward's products)
-        need = [max(lb.rs_gemm_workspace_size(kin, n, m), lb.rs_gemm_workspace_size(m, kin, n),
-                    lb.rs_col_sum_workspace_size(m, n)) for kin, n, m in shapes]
+        need = [gemm_need(shapes + [(m, kin, n) for kin, n, m in shapes])]  # dW and d_in orientations
+        need += [lb.rs_col_sum_workspace_size(m, n) for _, n, m in shapes]
         need += [lb.rs_prelu_rows_bwd_workspace_size(M, W.shape[1], T) for W in att.kernels]
         need += [lb.rs_prelu_rows_bwd_workspace_size(B, L.units, 1) for L in self.dense_layer]
         need += [lb.rs_dice_train_workspace_size(M, 4 * K)] if att.activation == "dice" else []
@@ -1080,8 +896,7 @@ class DIN(TowerMixin, KerasModule):
                      and lb.rs_din_att_prelu_bwd_workspace_size(B, T, 4 * K, *att.kernels[1].shape) >= 0)
         if att_fused:
             need.append(lb.rs_din_att_prelu_bwd_workspace_size(B, T, 4 * K, *att.kernels[1].shape))
-        gws = _gemm_ws(self, max(need))
-        gw = (ptr(gws), gws.numel())
+        gw = gemm_ws(self, max(need))
 
         # ---- forward, keeping what the backward needs
         hist_ids = [h.reshape(M, 1) for h in hists]
@@ -1138,9 +953,7 @@ class DIN(TowerMixin, KerasModule):
         for f in self.dense_feature_columns:
             x[:, col:col + 1] = _to_device_f32(inputs[f["feat"]], dev).reshape(B, 1)
             col += 1
-        mean, var, y0 = emp(width), emp(width), emp(B, width)
-        call("rs_bn_train_fwd", ptr(x), width, B, width, ptr(bn.gamma), ptr(bn.beta), bn.epsilon, 0.99,
-             ptr(bn.moving_mean), ptr(bn.moving_variance), ptr(mean), ptr(var), ptr(y0), width, st)
+        bn_saved, y0 = bn_train_fwd(bn, x, st)
         acts, pre, dsaved = [y0], [], []
         for L in self.dense_layer:
             z, y = emp(B, L.units), emp(B, L.units)
@@ -1161,23 +974,11 @@ class DIN(TowerMixin, KerasModule):
         logit = emp(B)
         call("rs_dense_fwd", ptr(acts[-1]), acts[-1].stride(0), ptr(out.kernel), ptr(out.bias), None,
              _lib.ACT[None], ptr(logit), 1, B, out.kernel.shape[0], 1, st)
-        g, g0 = emp(B), emp(B)
-        loss = emp(B) if return_loss else None
-        call("rs_head_grad", ptr(logit), ptr(logit), ptr(labels), B, 1.0, 0.0, ptr(g), ptr(g0), ptr(loss), st)
+        g, loss = bce_head_logit(logit, labels, return_loss, st)
 
         # ---- backward (every gradient before any update)
+        # (every Dense here: column sums on the workspace, rs_col_sum_split; PReLU / Dice below, so no mask)
         updates = []
-
-        def dense_back(W, bias, a_in, dz, m):
-            kin, n = W.shape
-            dW, db, din = emp(kin, n), emp(n), emp(m, kin)
-            call("rs_gemm", 1, 0, kin, n, m, 1.0, ptr(a_in), a_in.stride(0), ptr(dz), dz.stride(0), 0.0, ptr(dW), n,
-                 None, 0, *gw, st)
-            call("rs_col_sum_split", ptr(dz), dz.stride(0), m, n, ptr(db), *gw, st)
-            call("rs_gemm", 0, 1, m, kin, n, 1.0, ptr(dz), dz.stride(0), ptr(W), n, 0.0, ptr(din), kin, None, 0,
-                 *gw, st)
-            updates.extend([(W, dW), (bias, db)])
-            return din
 
         def prelu_back(z, dy, alpha, period, m):
             n = z.shape[1]
@@ -1193,7 +994,8 @@ class DIN(TowerMixin, KerasModule):
             updates.append((d.alphas, dal))
             return dx
 
-        dh = dense_back(out.kernel, out.bias, acts[-1], g.view(B, 1), B)
+        dW, db, dh = dense_backward(out.kernel, acts[-1], g.view(B, 1), gw, emp, st, split_sum=True)
+        updates.extend([(out.kernel, dW), (out.bias, db)])
         if rate > 0:
             rng.redraw(dh, rate, drop_off, st)
             rng.end_step(st)
@@ -1203,10 +1005,9 @@ class DIN(TowerMixin, KerasModule):
                 dz = dice_back(L.dice, pre[li], dsaved[li], dh, B, L.units)
             else:
                 dz = prelu_back(pre[li], dh, L.alpha, 1, B)
-            dh = dense_back(L.kernel, L.bias, acts[li], dz, B)
-        dx, dgam, dbet = emp(B, width), emp(width), emp(width)
-        call("rs_bn_train_bwd", ptr(x), width, B, width, ptr(mean), ptr(var), ptr(bn.gamma), bn.epsilon, ptr(dh),
-             dh.stride(0), ptr(dx), width, ptr(dgam), ptr(dbet), st)
+            dW, db, dh = dense_backward(L.kernel, acts[li], dz, gw, emp, st, split_sum=True)
+            updates.extend([(L.kernel, dW), (L.bias, db)])
+        dx, dgam, dbet = bn_train_bwd(bn, x, bn_saved, dh, st)
         updates.extend([(bn.gamma, dgam), (bn.beta, dbet)])
         ds, dseq = emp(M), emp(M, K)
         call("rs_masked_softmax_pool_bwd", ptr(a), ptr(h_first), _lib.id_kind(h_first), h_first.stride(0), ptr(seq),
@@ -1222,34 +1023,26 @@ class DIN(TowerMixin, KerasModule):
                  st)
             updates.extend(zip([W1, b1, al1, W2, b2, al2, att.out_kernel, att.out_bias], gr))
         else:
-            dh3 = dense_back(att.out_kernel, att.out_bias, hl, ds.view(M, 1), M)
+            dW, db, dh3 = dense_backward(att.out_kernel, hl, ds.view(M, 1), gw, emp, st, split_sum=True)
+            updates.extend([(att.out_kernel, dW), (att.out_bias, db)])
             for li in reversed(range(len(att.kernels))):
                 dz = prelu_back(att_pre[li], dh3, att.alphas[li], T, M)
-                dh3 = dense_back(att.kernels[li], att.biases[li], att_in[li], dz, M)
+                dW, db, dh3 = dense_backward(att.kernels[li], att_in[li], dz, gw, emp, st, split_sum=True)
+                updates.extend([(att.kernels[li], dW), (att.biases[li], db)])
         for li in reversed(range(len(att.dice))):
             dh3 = dice_back(att.dice[li], att_in[li], att_pre[li], dh3, M, 4 * K)
         call("rs_din_att_concat_bwd", ptr(dh3), ptr(item), ptr(seq), B, T, K, ptr(dx) + 4 * K, width, ptr(dseq), st)
 
         # ---- SGD
         _lib.sgd_update_multi([(w, gr, gr.numel(), 0.0) for w, gr in updates], lr, st)
-        ws_n = _lib.lib().rs_embedding_sgd_workspace_size(M)
-        ws = self.__dict__.get("_emb_ws")
-        if ws is None or ws.numel() < ws_n:
-            ws = self.__dict__["_emb_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=dev)
-
-        def emb_sgd(layer, ids, grad_ptr, ldg, rows):
-            call("rs_embedding_sgd", ptr(layer.table), layer.total_rows, layer.k, ptr(ids), _lib.id_kind(ids),
-                 ids.stride(0), ptr(layer.field_offsets), ptr(layer.field_vocab), 1, rows, grad_ptr, ldg, float(lr),
-                 ptr(ws), None, st)
-
-        col = 0
+        col = 0  # (each table is a one-field EmbedLayer; the history's [B*T, 1] ids come first and size _emb_ws)
         for i, layer in enumerate(self.embed_seq_layers):
-            emb_sgd(layer, hist_ids[i], ptr(dseq) + 4 * col, K, M)
-            emb_sgd(layer, cand_ids[i], ptr(dx) + 4 * (K + col), width, B)
+            embedding_sgd(layer, hist_ids[i], ptr(dseq) + 4 * col, K, lr, st, self)
+            embedding_sgd(layer, cand_ids[i], ptr(dx) + 4 * (K + col), width, lr, st, self)
             col += layer.k
         col = 2 * K
         for layer, ids in zip(self.embed_sparse_layers, other_ids):
-            emb_sgd(layer, ids, ptr(dx) + 4 * col, width, B)
+            embedding_sgd(layer, ids, ptr(dx) + 4 * col, width, lr, st, self)
             col += layer.k
         self._weights_changed()
         for L in list(self.embed_seq_layers) + list(self.embed_sparse_layers):
@@ -1335,33 +1128,21 @@ class NFM(TowerMixin, KerasModule):
         x = self.bi_interaction_input(inputs, check_ids)  # [B, nd + k]
         rows = e.gather(ids, check_ids=False)             # [B, F*k] (ids checked above)
         D = self.nd + k
-        mean, var, y0 = emp(D), emp(D), emp(B, D)
-        call("rs_bn_train_fwd", ptr(x), D, B, D, ptr(bn.gamma), ptr(bn.beta), bn.epsilon, 0.99, ptr(bn.moving_mean),
-             ptr(bn.moving_variance), ptr(mean), ptr(var), ptr(y0), D, st)
+        bn_saved, y0 = bn_train_fwd(bn, x, st)
         layers = self._layers()
         acts, drop = _dnn_train_forward(self, dnn, y0, rate, st)
         acts.append(dnn.output_layer(acts[-1]))
         logit = emp(B)
         call("rs_dense_fwd", ptr(acts[-1]), acts[-1].stride(0), ptr(out.kernel), ptr(out.bias), None,
              _lib.ACT[None], ptr(logit), 1, B, out.kernel.shape[0], 1, st)
-        g, g0 = emp(B), emp(B)
-        loss = emp(B) if return_loss else None
-        call("rs_head_grad", ptr(logit), ptr(logit), ptr(labels), B, 1.0, 0.0, ptr(g), ptr(g0), ptr(loss), st)
-        gws = _gemm_ws(self, max(_lib.lib().rs_gemm_workspace_size(L.kernel.shape[0], L.kernel.shape[1], B)
-                                 for L in layers))
-        grads, delta = _dnn_backward(layers, acts, g.view(B, 1), (ptr(gws), gws.numel()), emp, st, drop=drop)
-        dx, dgam, dbet = emp(B, D), emp(D), emp(D)
-        call("rs_bn_train_bwd", ptr(x), D, B, D, ptr(mean), ptr(var), ptr(bn.gamma), bn.epsilon, ptr(delta),
-             delta.stride(0), ptr(dx), D, ptr(dgam), ptr(dbet), st)
+        g, loss = bce_head_logit(logit, labels, return_loss, st)
+        gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in layers]))
+        grads, delta = _dnn_backward(layers, acts, g.view(B, 1), gw, emp, st, drop=drop)
+        dx, dgam, dbet = bn_train_bwd(bn, x, bn_saved, delta, st)
         de = emp(B, F * k)
         call("rs_bi_interaction_bwd", ptr(rows), F * k, ptr(dx) + 4 * self.nd, D, F, k, B, ptr(de), F * k, st)
         _lib.sgd_update_multi(_dnn_updates(grads) + [(bn.gamma, dgam, D, 0.0), (bn.beta, dbet, D, 0.0)], lr, st)
-        ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * F)
-        ws = self.__dict__.get("_emb_ws")
-        if ws is None or ws.numel() < ws_n:
-            ws = self.__dict__["_emb_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=dev)
-        call("rs_embedding_sgd", ptr(e.table), e.total_rows, k, ptr(ids), _lib.id_kind(ids), ids.stride(0),
-             ptr(e.field_offsets), ptr(e.field_vocab), F, B, ptr(de), F * k, float(lr), ptr(ws), None, st)
+        embedding_sgd(e, ids, ptr(de), F * k, lr, st, self)
         self._weights_changed()
         return loss
 
@@ -1405,11 +1186,7 @@ class FFM(KerasModule):
         gradient comes from the pre-step weights.  Returns per-sample losses
         (before the step) if ``return_loss``."""
         L = self.ffm
-        if isinstance(inputs, (tuple, list)):
-            dense, ids = _to_device_f32(inputs[0], self._dev), _ids_tensor(inputs[1], self._dev)
-        else:
-            X = _to_device_f32(inputs, self._dev)
-            dense, ids = X[:, :L.nd], X[:, L.nd:]
+        dense, ids = _split_criteo(inputs, L.nd, self._dev)
         labels = _to_device_f32(labels, self._dev).reshape(-1)
         B, F, k, nd, st, dev = ids.shape[0], len(L.onehot_dims), L.k, L.nd, _lib.stream(), self._dev
         E = L.field_num * k
@@ -1419,8 +1196,7 @@ class FFM(KerasModule):
         call("rs_ffm_train_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense), dense.stride(0), nd,
              ptr(L.v), ptr(L.w), ptr(L.w0), ptr(L.field_offsets), ptr(L.field_vocab), F, k, ptr(labels), B, ptr(G),
              ptr(g), ptr(loss), st)
-        gws = _gemm_ws(self, max(_lib.lib().rs_gemm_workspace_size(nd, E, B), _lib.lib().rs_gemm_workspace_size(nd, 1, B)))
-        gw = (ptr(gws), gws.numel())
+        gw = gemm_ws(self, gemm_need([(nd, E, B), (nd, 1, B)]))
         dvd, dwd, dw0 = emp(max(nd, 1), E), emp(max(nd, 1)), emp(1)
         if nd:
             call("rs_gemm", 1, 0, nd, E, B, 1.0, ptr(dense), dense.stride(0), ptr(G), E, 0.0, ptr(dvd), E, None, 0,
@@ -1434,15 +1210,8 @@ class FFM(KerasModule):
         _lib.sgd_update_multi(([(L.v, dvd, nd * E, 0.0), (L.w, dwd, nd, 0.0)] if nd else []) + [(L.w0, dw0, 1, 0.0)],
                               lr, st)
         n_sparse = L.feature_num - nd
-        ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * F)
-        ws = self.__dict__.get("_emb_ws")
-        if ws is None or ws.numel() < ws_n:
-            ws = self.__dict__["_emb_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=dev)
-        call("rs_embedding_sgd_strided", ptr(L.v) + 4 * nd * E, n_sparse, E, ptr(ids), _lib.id_kind(ids),
-             ids.stride(0), ptr(L.field_offsets), ptr(L.field_vocab), F, B, ptr(G), E, 0, float(lr), ptr(ws), None,
-             st)
-        call("rs_embedding_sgd_strided", ptr(L.w) + 4 * nd, n_sparse, 1, ptr(ids), _lib.id_kind(ids), ids.stride(0),
-             ptr(L.field_offsets), ptr(L.field_vocab), F, B, ptr(g), 1, 0, float(lr), ptr(ws), None, st)
+        embedding_sgd_strided(ptr(L.v) + 4 * nd * E, n_sparse, E, ids, L.field_offsets, L.field_vocab, G, lr, st, self)
+        embedding_sgd_strided(ptr(L.w) + 4 * nd, n_sparse, 1, ids, L.field_offsets, L.field_vocab, g, lr, st, self)
         self._weights_changed()
         return loss
 
@@ -1616,11 +1385,7 @@ class DeepCrossing(KerasModule):
         nh, nu = len(self.hidden_units), len(units)
         emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         all_layers = self._all_layers()
-        gws = _gemm_ws(self, max(_lib.lib().rs_gemm_workspace_size(L.kernel.shape[0], L.kernel.shape[1], B)
-                                 for L in all_layers))
-        gw = (ptr(gws), gws.numel())
-        g, g0 = emp(B), emp(B)
-        loss = emp(B) if return_loss else None
+        gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in all_layers]))
         if fused:
             ci = (C.c_int * nh)(*self.hidden_units)
             widths = self.hidden_units + [d]
@@ -1633,7 +1398,7 @@ class DeepCrossing(KerasModule):
                  ptr(saved), ptr(prob), ptr(logit), B, ptr(self._err.t), st)
             if check_ids:
                 self._err.check("DeepCrossing.train_step")
-            call("rs_head_grad", ptr(logit), ptr(logit), ptr(labels), B, 1.0, 0.0, ptr(g), ptr(g0), ptr(loss), st)
+            g, loss = bce_head_logit(logit, labels, return_loss, st)
             call("rs_res_tower_bwd", ptr(saved), d, nh, ci, nu, ptr(self.prepared_bwd()), None, 0, ptr(g),
                  ptr(deltas), ptr(dx0), d, B, st)
             # views of saved / deltas: x_u and a_{u,l}, delta_{u,l}
@@ -1650,16 +1415,10 @@ class DeepCrossing(KerasModule):
             grads = []
             for u, layers in enumerate(units):
                 for l, L in enumerate(layers):
-                    a_in, dl = (xs[u] if l == 0 else acts[u][l - 1]), dels[u][l]
-                    K_in, N_out = L.kernel.shape
-                    dW, db = emp(K_in, N_out), emp(N_out)
-                    call("rs_gemm", 1, 0, K_in, N_out, B, 1.0, ptr(a_in), a_in.stride(0), ptr(dl), dl.stride(0), 0.0,
-                         ptr(dW), N_out, None, 0, *gw, st)
-                    call("rs_col_sum", ptr(dl), dl.stride(0), B, N_out, ptr(db), st)
+                    a_in = xs[u] if l == 0 else acts[u][l - 1]
+                    dW, db, _ = dense_backward(L.kernel, a_in, dels[u][l], gw, emp, st, d_in=False)
                     grads.append((L, dW, db))
-            dWh, dbh = emp(d, 1), emp(1)
-            call("rs_gemm", 1, 0, d, 1, B, 1.0, ptr(xs[nu]), d, ptr(g), 1, 0.0, ptr(dWh), 1, None, 0, *gw, st)
-            call("rs_col_sum", ptr(g), 1, B, 1, ptr(dbh), st)
+            dWh, dbh, _ = dense_backward(head.kernel, xs[nu], g.view(B, 1), gw, emp, st, d_in=False)
             grads.append((head, dWh, dbh))
         else:
             x = e.gather(ids, dense if self.nd else None, check_ids=check_ids)
@@ -1673,7 +1432,7 @@ class DeepCrossing(KerasModule):
             logit = emp(B)
             call("rs_dense_fwd", ptr(xs[-1]), xs[-1].stride(0), ptr(head.kernel), ptr(head.bias), None, _lib.ACT[None],
                  ptr(logit), 1, B, d, 1, st)
-            call("rs_head_grad", ptr(logit), ptr(logit), ptr(labels), B, 1.0, 0.0, ptr(g), ptr(g0), ptr(loss), st)
+            g, loss = bce_head_logit(logit, labels, return_loss, st)
             grads, dy = _dnn_backward([head], [xs[-1]], g.view(B, 1), gw, emp, st)
             for u in reversed(range(nu)):
                 eu = dy * (xs[u + 1] > 0)
@@ -1682,7 +1441,7 @@ class DeepCrossing(KerasModule):
                 dy = eu + below
             dx0 = dy
         _dnn_apply(grads, lr, st)
-        _embedding_sgd(self, ids, dx0, dx0.stride(0), lr, st)
+        embedding_sgd(e, ids, ptr(dx0) + 4 * self.nd, dx0.stride(0), lr, st, self)
         self._weights_changed()
         return loss
 
@@ -1785,26 +1544,16 @@ class WideDeep(KerasModule):
         emb = e.gather(ids, check_ids=check_ids)  # [B, F*k]: the deep input has no dense block
         acts, drop = _dnn_train_forward(self, deep, emb, rate, st)
         deep_out = deep.output_layer(acts[-1])
-        g_w, g_d = emp(B), emp(B)
-        loss = emp(B) if return_loss else None
-        call("rs_head_grad", ptr(wide), ptr(deep_out), ptr(labels), B, 0.5, 0.5, ptr(g_w), ptr(g_d), ptr(loss), st)
+        g_w, g_d, loss = bce_head(wide, deep_out, labels, 0.5, 0.5, return_loss, st)
         n = self.wide.w.shape[0]
-        gws = _gemm_ws(self, max([_lib.lib().rs_gemm_workspace_size(L.kernel.shape[0], L.kernel.shape[1], B)
-                                  for L in layers] + [_lib.lib().rs_gemm_workspace_size(n, 1, B)]))
-        gw = (ptr(gws), gws.numel())
+        gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in layers] + [(n, 1, B)]))
         grads, demb = _dnn_backward(layers, acts, g_d.view(B, 1), gw, emp, st, drop=drop)
         dw0 = emp(1)
         call("rs_col_sum", ptr(g_w), 1, B, 1, ptr(dw0), st)
         # updates (every gradient above and in wide_update comes from the pre-step weights)
         _lib.sgd_update_multi(_dnn_updates(grads) + wide_update(g_w, gw, emp, st) + [(self.wide.w0, dw0, 1, 0.0)],
                               lr, st)
-        Fk = e.n_fields * e.k
-        ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * e.n_fields)
-        ws = self.__dict__.get("_emb_ws")
-        if ws is None or ws.numel() < ws_n:
-            ws = self.__dict__["_emb_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=dev)
-        call("rs_embedding_sgd", ptr(e.table), e.total_rows, e.k, ptr(ids), _lib.id_kind(ids), ids.stride(0),
-             ptr(e.field_offsets), ptr(e.field_vocab), e.n_fields, B, ptr(demb), Fk, float(lr), ptr(ws), None, st)
+        embedding_sgd(e, ids, ptr(demb), e.n_fields * e.k, lr, st, self)
         self._weights_changed()
         return loss
 
@@ -1871,12 +1620,7 @@ class WideDeep(KerasModule):
                      *gw, st)
                 ups = [(ptr(w), dwd, nd, 0.0), (ptr(w) + 4 * nd, dwd, nd, 0.0)]
             call("rs_l2_decay", ptr(w), n, float(lr), float(self.wide.w_reg), st)
-            ws_n = _lib.lib().rs_embedding_sgd_workspace_size(B * F)
-            ws = self.__dict__.get("_wide_ws")
-            if ws is None or ws.numel() < ws_n:
-                ws = self.__dict__["_wide_ws"] = torch.empty(ws_n, dtype=torch.uint8, device=dev)
-            call("rs_embedding_sgd_strided", ptr(w) + 4 * 2 * nd, n - 2 * nd, 1, ptr(ids), _lib.id_kind(ids),
-                 ids.stride(0), ptr(offs), ptr(wid), F, B, ptr(g), 1, 0, float(lr), ptr(ws), None, st)
+            embedding_sgd_strided(ptr(w) + 4 * 2 * nd, n - 2 * nd, 1, ids, offs, wid, g, lr, st, self, "_wide_ws")
             return ups
 
         return self._train(wide, wide_update, ids, labels, lr, return_loss, check_ids, dropout)

@@ -40,6 +40,8 @@ import torch.distributed as dist
 
 from . import _lib
 from ._lib import call, ptr
+from ._train_ops import (_Dropout, _dnn_backward, _dnn_train_forward, _dropout_rate, _split_criteo, fm_backward, fm_xv,
+                         gemm_need)
 
 
 _FLAG_BITS = 8  # rs_flag bits carried across ranks
@@ -413,7 +415,6 @@ class HipShardOps:
         gradient; returns dL/dx [B, d].  drop = (_Dropout, rate, offsets):
         DNNLayer's Dropout draws of the hidden layers (rs_dropout), reused in
         the backward."""
-        from .models import _dnn_backward
         sh, st = model.emb, _lib.stream()
         B, d, kfm = dense.shape[0], sh.d, sh.kfm
         x = tb["x"]
@@ -421,28 +422,20 @@ class HipShardOps:
              ptr(got), ptr(rb["zoff"]), ptr(rb["nslots"]), model.F, model.k, ptr(x), d, B, ptr(self.err), st)
         dnn = model.dnn
         layers = list(dnn.hidden_layer) + [dnn.output_layer]
-        acts = [x]
-        for i, layer in enumerate(dnn.hidden_layer):
-            a = layer(acts[-1])
-            if drop is not None:
-                drop[0].redraw(a, drop[1], drop[2][i], st)
-            acts.append(a)
+        acts, _ = _dnn_train_forward(model, dnn, x, 0.0, st, drop=drop)  # the masks at _draws' offsets
         dnn_out = dnn.output_layer(acts[-1])
         fm_out = tb["fm"]
         # FMLayer on the dense x: its own packed image (nd = d, no fields)
         call("rs_fm_prepare", ptr(sh.w1), ptr(sh.v), d, 0, 0, kfm, ptr(tb["fm_prep"]), st)
         call("rs_fm_fwd", ptr(x), d, d, ptr(tb["fm_prep"]), ptr(sh.w0), kfm, ptr(fm_out), B, st)
         gw = (ptr(tb["gemm_ws"]), tb["gemm_ws"].numel())
-        s = tb["s"]
-        call("rs_gemm", 0, 0, B, kfm, d, 1.0, ptr(x), d, ptr(sh.v), kfm, 0.0, ptr(s), kfm, None, 0, *gw, st)
+        s = fm_xv(x, sh.v, gw, st, out=tb["s"])
         g_fm, g_dnn = tb["g_fm"], tb["g_dnn"]
         call("rs_head_grad_scaled", ptr(fm_out), ptr(dnn_out), ptr(labels), B, 0.5, 0.5, float(scale), ptr(g_fm),
              ptr(g_dnn), ptr(loss), st)
         emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
         _, dx = _dnn_backward(layers, acts, g_dnn.view(B, 1), gw, emp, st, outs=tb["dnn_views"], drop=drop)
-        call("rs_fm_x_grad", ptr(x), d, ptr(s), ptr(sh.w1), ptr(sh.v), B, d, kfm, ptr(g_fm), ptr(dx), d, st)
-        call("rs_fm_param_grads", ptr(x), d, ptr(s), ptr(sh.v), B, d, kfm, ptr(g_fm), ptr(tb["dw1"]), ptr(tb["dv"]),
-             ptr(tb["dw0"]), st)
+        fm_backward(x, s, sh.w1, sh.v, g_fm, dx, st, outs=(tb["dw1"], tb["dv"], tb["dw0"]))
         return dx
 
     def dedup_route(self, sh, ids, rb):
@@ -1259,7 +1252,6 @@ class ShardedDeepFM:
         """DeepFM outputs of a sequence of local batches [(dense, ids), ...],
         pipelined: batch t+1's exchange overlaps batch t's fused kernel.
         Every rank must pass the same number of batches."""
-        from .models import _split_criteo
         batches = [_split_criteo(b, self.nd, self.device) for b in batches]
         outs = [torch.empty(d.shape[0], 1, dtype=torch.float32, device=self.device) for d, _ in batches]
         if not batches:
@@ -1332,8 +1324,7 @@ class ShardedDeepFM:
                   "svocab": torch.full((S,), max(sh.table_shard.shape[0], 1), dtype=torch.int64, device=dev)}
             if isinstance(self.ops, HipShardOps):
                 lib = _lib.lib()
-                gmax = max(lib.rs_gemm_workspace_size(K, N, B) for _, (K, N) in layers)
-                gmax = max(gmax, lib.rs_gemm_workspace_size(B, kfm, d))
+                gmax = gemm_need([(K, N, B) for _, (K, N) in layers] + [(B, kfm, d)])
                 tb["gemm_ws"] = torch.empty(max(gmax, 1), dtype=torch.uint8, device=dev)
                 tb["fm_prep"] = torch.empty(lib.rs_fm_prepared_size(d, 0, 0, kfm), dtype=torch.float32, device=dev)
                 tb["emb_ws"] = torch.empty(max(lib.rs_embedding_sgd_workspace_size(n_look), 1), dtype=torch.uint8,
@@ -1344,7 +1335,6 @@ class ShardedDeepFM:
     def _dropout(self):
         """The rank's Dropout generator (rs_dropout): seeded from the model
         seed and the rank (dropout_seed), so ranks draw independent masks."""
-        from .models import _Dropout
         if getattr(self, "_drop_rng", None) is None:
             self._drop_rng = _Dropout(dropout_seed(self._seed, self.rank), self.device)
         return self._drop_rng
@@ -1378,7 +1368,6 @@ class ShardedDeepFM:
         training mode (rate = the layer's, dropout=False turns it off) with
         counter-based masks drawn per rank (_dropout).  Returns the per-sample
         losses of the local batch (before the step) if ``return_loss``."""
-        from .models import _split_criteo, _dropout_rate
         from .layers import _to_device_f32
         sh = self.emb
         rate = _dropout_rate(self.dnn, dropout)
@@ -1422,7 +1411,6 @@ class ShardedDeepFM:
         return loss
 
     def forward(self, inputs, check=True, out=None):
-        from .models import _split_criteo
         sh = self.emb
         if isinstance(inputs, (tuple, list)) and not isinstance(self.ops, HipShardOps):
             dense, ids = inputs  # CPU test double: host tensors as given

@@ -94,3 +94,32 @@ def test_attention_dice_has_no_dense():
     w = att.keras_weights()
     assert not any(k.startswith("dense_") for k in w)
     assert w["dice_0/dice_alpha"].shape == (32,) and w["out/kernel"].shape == (32, 1)
+
+
+def test_scratch_is_one_grow_only_buffer_per_owner_and_name():
+    """_train_ops.scratch: the first call allocates, a smaller request returns
+    the same tensor object, a larger one a larger tensor, and two names on
+    one owner are independent."""
+    from recommender_system_amd._train_ops import scratch
+    owner = Dense(3, device=DEV, seed=0)  # any module with a device; its buffers live in owner.__dict__
+    a = scratch(owner, "_emb_ws", 100)
+    assert a.dtype == torch.uint8 and a.numel() == 100 and a.device.type == "cpu"
+    assert owner.__dict__["_emb_ws"] is a
+    assert scratch(owner, "_emb_ws", 40) is a and scratch(owner, "_emb_ws", 100) is a
+    b = scratch(owner, "_emb_ws", 101)
+    assert b is not a and b.numel() == 101 and owner.__dict__["_emb_ws"] is b
+    c = scratch(owner, "_gemm_wsbuf", 7)
+    assert c.numel() == 7 and scratch(owner, "_emb_ws", 1) is b and scratch(owner, "_gemm_wsbuf", 7) is c
+
+
+def test_dropout_take_rounds_to_counters_and_rel_accumulates():
+    """_Dropout.take: every range starts at a multiple of 4 elements (one
+    Philox counter gives 4) and ``rel`` is the running total; ``offset`` adds
+    the device counter."""
+    from recommender_system_amd import models as M
+    rng = M._Dropout(2 ** 64 + 5, device=DEV)
+    assert rng.seed == 5 and rng.rel == 0 and int(rng.base) == 0
+    assert [rng.take(n) for n in (1, 4, 5, 0, 33 * 32)] == [0, 4, 8, 16, 16]
+    assert rng.rel == 16 + 33 * 32 and rng.offset == rng.rel
+    rng.base += 40  # what end_step's rs_dropout_advance does on the device
+    assert rng.take(3) == 16 + 33 * 32 and rng.offset == 40 + 16 + 33 * 32 + 4
