@@ -54,8 +54,8 @@ enum rs_act {
 
 /* Bits of the device error flag (int, caller-owned, zero it before use):
  * kernels OR these in; the host layer raises IndexError for RS_FLAG_BAD_ID
- * (TF's InvalidArgumentError on an out-of-range Embedding id) and RSError for
- * any other bit. */
+ * (TF's InvalidArgumentError on an out-of-range Embedding id; its BadIdError
+ * is an IndexError and an RSError) and a plain RSError for any other bit. */
 enum rs_flag {
   RS_FLAG_BAD_ID = 1, /* an id outside [0, vocab) (its row read as zeros)               */
   RS_FLAG_LAYOUT = 2, /* field row ranges overlap or decrease where a kernel needs the
@@ -1233,6 +1233,36 @@ int rs_embedding_sgd(float* table, int64_t n_rows, int k, const void* ids,
                      int n_fields, int64_t batch, const float* grad,
                      int64_t grad_stride, float lr, void* workspace,
                      int* err_flag, rs_stream_t stream);
+/* AFM training (compile_fit on AFM, utils/compile_fit.py:9-15 on
+ * model/afm.py:15-18; AFM.train_step composes it with rs_gemm / rs_col_sum /
+ * rs_sgd_update_multi / rs_embedding_sgd): rs_afm_train_fwd is
+ * rs_embed_pair_pool_fwd's forward (same ids / table / mode arguments: mode 0
+ * sum = 'att', 1 mean = 'avg', 2 max, n_fields <= 32 for max; 1 <= k <= 64)
+ * AND the backward down to the rows, in one launch with the rows in
+ * registers.  With x = the pooled pair products, z = x.head_w + head_b[0],
+ * s = sigmoid(z) and u = the input of the last of the n_sigmoid (1 or 2)
+ * sigmoids (u = z, or u = s: Keras takes it as the BCE logit):
+ *   pooled[b*pooled_stride + c] = x_c;  prob[b] = sigmoid(u) (optional);
+ *   loss[b] = max(u,0) - u t + log1p(exp(-|u|)) (optional), t = labels[b];
+ *   g[b] = dL/dz = (sigmoid(u) - t)/batch, times s(1-s) with two sigmoids;
+ *   drows[b*drows_stride + f*k + c] = dL/d(row of field f)_c, the layout
+ *   rs_embedding_sgd reads: g w_c (S_c - e_fc) with S = sum_f e_f (sum), the
+ *   same / P (mean), or for max g w_c e_{j*}c at i*, g w_c e_{i*}c at j* and 0
+ *   elsewhere, (i*, j*) the arg-max pair of (b, c) — a tie goes to the first
+ *   pair in row-major order (TF splits it evenly among the tied pairs).
+ * Every element of drows[b, 0 : n_fields*k] is written (no pre-zeroing); one
+ * field has no pair (x = 0, drows = 0, g still produced).  An out-of-range id
+ * is the forward's zero row: it sets RS_FLAG_BAD_ID and its own block of
+ * drows is 0.  dL/dhead_w = pooled^T g and dL/dhead_b = sum_b g are left to
+ * rs_gemm / rs_col_sum.  No atomics: run-to-run bit-identical.              */
+int rs_afm_train_fwd(const void* ids, int id_kind, int64_t id_stride,
+                     const float* table, const int64_t* field_offsets,
+                     const int64_t* field_vocab, int n_fields, int k, int mode,
+                     const float* head_w, const float* head_b, int n_sigmoid,
+                     const float* labels, int64_t batch, float* pooled,
+                     int64_t pooled_stride, float* prob, float* g, float* loss,
+                     float* drows, int64_t drows_stride, int* err_flag,
+                     rs_stream_t stream);
 
 /* -------------------------------------- row-sharded lookup (§8(e), cfg 5)
  * Global row of (b,c) = field_offsets[c] + id(b,c).  Rows are split across

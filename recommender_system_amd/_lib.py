@@ -176,6 +176,7 @@ SIGNATURES = {
     "rs_embedding_sgd_strided": (I, [P, L, I, P, I, L, P, P, I, L, P, L, L, F, P, P, P]),
     "rs_ffm_train_fwd": (I, [P, I, L, P, L, I, P, P, P, P, P, I, I, P, L, P, P, P, P]),
     "rs_l2_decay": (I, [P, L, F, F, P]),
+    "rs_afm_train_fwd": (I, [P, I, L, P, P, P, I, I, I, P, P, I, P, L, P, L, P, P, P, P, L, P, P]),
     "rs_fm_partial_width": (I, [I]),
     "rs_embed_pair_pool_fwd": (I, [P, I, L, P, P, P, I, I, I, P, L, I, P, L, I, P, P, I, P, L, P, P]),
     "rs_pair_products_fwd": (I, [P, L, I, I, L, P, P]),
@@ -218,6 +219,12 @@ _lib = None
 
 class RSError(RuntimeError):
     pass
+
+
+class BadIdError(RSError, IndexError):
+    """RS_FLAG_BAD_ID alone: an embedding id outside [0, vocab).  An
+    IndexError, as TF's Embedding raises, and an RSError like every other
+    failure the library reports."""
 
 
 _ALLOW_MISSING = False  # scripts only: bind an older build that lacks newer entries

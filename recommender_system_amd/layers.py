@@ -76,7 +76,8 @@ def _ids_tensor(ids, device):
 
 class _ErrFlag:
     """Device int flag the kernels OR rs_flag bits into: an out-of-range id
-    (IndexError, as TF's Embedding raises) or a kernel-internal failure."""
+    (BadIdError: an IndexError, as TF's Embedding raises) or a kernel-internal
+    failure (RSError)."""
 
     def __init__(self, device):
         self.t = torch.zeros(1, dtype=torch.int32, device=device)
@@ -87,7 +88,7 @@ class _ErrFlag:
             self.t.zero_()
             if v & ~_lib.FLAG_BAD_ID:
                 raise _lib.RSError(f"{what}: kernel error flag {v:#x} ({_lib.flag_names(v)})")
-            raise IndexError(f"{what}: embedding id out of range (indices must be in [0, vocab))")
+            raise _lib.BadIdError(f"{what}: embedding id out of range (indices must be in [0, vocab))")
 
 
 def _glorot_uniform(fan_in, fan_out, gen, device):

@@ -50,7 +50,7 @@ from ._lib import call, ptr
 from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense, DNNLayer, EmbedLayer, FFMLayer,
                      FGCNNLayer, FMLayer, InnerProductLayer, OuterProductLayer,
                      KerasModule, ResLayer, TowerMixin, WideLayer, sigmoid_combine, _ids_tensor, _to_device_f32,
-                     _ErrFlag, _RES_MAXH, _RES_MAXU, _res_key, _res_ok, _res_prepare, mmoe_layer, tower_layer,
+                     _AFM_MODES, _ErrFlag, _RES_MAXH, _RES_MAXU, _res_key, _res_ok, _res_prepare, mmoe_layer, tower_layer,
                      _MMOE_MAXL, _mmoe_dims, _mmoe_input, _mmoe_ok, _mmoe_params, _mmoe_prepare)
 
 
@@ -1158,6 +1158,46 @@ class AFM(KerasModule):
 
     def forward(self, inputs, check_ids=True):
         return self.afm_layer.pooled(inputs, check_ids, n_sigmoid=2)[1]
+
+    def train_step(self, inputs, labels, lr=0.01, return_loss=False, check_ids=True):
+        """One step of compile_fit on AFM (utils/compile_fit.py:9-15 on
+        model/afm.py:15-18): BCE on the input of AFM.call's second sigmoid
+        (Keras takes it as the logit), plain SGD, no regulariser.
+          rs_afm_train_fwd: ids -> rows -> pooled pairs -> Dense(1) -> both
+          sigmoids -> g = dL/d(Dense output) -> dL/d(row) of every looked-up
+          row, one launch; the id check (``check_ids``: it raises before any
+          weight changes); dW = pooled^T g (rs_gemm) and db = sum g
+          (rs_col_sum); one rs_sgd_update_multi for the Dense(1); row-sparse
+          rs_embedding_sgd.
+        'att' pools by the sum (AttentionLayer's softmax runs over a size-1
+        axis), so attention_w / attention_h get an exactly zero gradient and
+        stay as they are.  'max' sends a tie's gradient to the first tied pair
+        in row-major order (TF splits it evenly).  ``inputs`` as in forward.
+        Returns the per-sample losses before the step if ``return_loss``."""
+        if self._dev.type != "cuda":
+            raise NotImplementedError("AFM.train_step: training runs only on a HIP device")
+        layer = self.afm_layer
+        if isinstance(inputs, (tuple, list)):
+            ids = _ids_tensor(inputs[1], self._dev)
+        else:
+            ids = _to_device_f32(inputs, self._dev)[:, layer.nd:]
+        labels = _to_device_f32(labels, self._dev).reshape(-1)
+        e, head = layer.embed_layer, layer.output_layer
+        B, F, k, st = ids.shape[0], e.n_fields, layer.k, _lib.stream()
+        emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self._dev)
+        pooled, g, de = emp(B, k), emp(B), emp(B, F * k)
+        loss = emp(B) if return_loss else None
+        call("rs_afm_train_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(e.table), ptr(e.field_offsets),
+             ptr(e.field_vocab), F, k, _AFM_MODES.get(layer.mode, 0), ptr(head.kernel), ptr(head.bias), 2,
+             ptr(labels), B, ptr(pooled), k, None, ptr(g), ptr(loss), ptr(de), F * k, ptr(layer._err.t), st)
+        if check_ids:
+            layer._err.check("AFM.train_step")
+        gw = gemm_ws(self, gemm_need([(k, 1, B)]))
+        dW, db, _ = dense_backward(head.kernel, pooled, g.view(B, 1), gw, emp, st, d_in=False)
+        _lib.sgd_update_multi([(head.kernel, dW, k, 0.0), (head.bias, db, 1, 0.0)], lr, st)
+        embedding_sgd(e, ids, ptr(de), F * k, lr, st, self)
+        self._weights_changed()
+        return loss
 
 
 class FFM(KerasModule):

@@ -7,8 +7,8 @@ reference's X (dataset.criteo_compact / an RSCB file): dense [N, nd], label
 codes [N, F], labels [N], per-field vocab.  Each batch is one
 ``model.train_step``: ``FM`` (rs_fm_train_step; the one-hot X of
 model/fm.py), ``DeepFM`` (model/deepFM.py), ``DCN`` (model/dcn.py), ``NFM``
-(model/nfm.py), ``FFM`` (model/ffm.py) or ``DeepCrossing``
-(model/deepCrossing.py) on dense + label-encoded X, ``WideDeep``
+(model/nfm.py), ``FFM`` (model/ffm.py), ``AFM`` (model/afm.py) or
+``DeepCrossing`` (model/deepCrossing.py) on dense + label-encoded X, ``WideDeep``
 (model/wideDeep.py) on the compact form of its packed row
 (``WideDeep.train_step_onehot``), and ``DIN`` (model/din.py:106) on the reference's input dict (pass it as
 ``dense``, ``ids=None``; every value is sliced along its first axis).
@@ -18,20 +18,20 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .models import DCN, DIN, FFM, FM, NFM, DeepCrossing, DeepFM, WideDeep
+from .models import AFM, DCN, DIN, FFM, FM, NFM, DeepCrossing, DeepFM, WideDeep
 
 
 def compile_fit(model, dense, ids, labels, field_vocab=None, batch_size=32, epochs=10, sgd=0.01, device=None):
-    """Train ``model`` (models.FM / DeepFM / DCN / NFM / FFM / DeepCrossing /
-    WideDeep / DIN) in place;
+    """Train ``model`` (models.FM / DeepFM / DCN / NFM / FFM / AFM /
+    DeepCrossing / WideDeep / DIN) in place;
     returns the per-epoch mean cross-entropy (before each step, without the l2
     terms).  ``field_vocab`` (feat_onehot_dim per field) is needed for FM's
     one-hot layout; the others read it from their layers (WideDeep's one-hot
     widths are ``field_vocab``, or its embedding layer's vocab when that is
     not given; the offsets are their cumulative sum).  PNN trains with its
     own loop in the reference (model/pnn.py:74-81): PNN.train_step."""
-    if not isinstance(model, (FM, DeepFM, DCN, NFM, FFM, DeepCrossing, WideDeep, DIN)):
-        raise NotImplementedError("compile_fit: FM, DeepFM, DCN, NFM, FFM, DeepCrossing, WideDeep and DIN "
+    if not isinstance(model, (FM, DeepFM, DCN, NFM, FFM, AFM, DeepCrossing, WideDeep, DIN)):
+        raise NotImplementedError("compile_fit: FM, DeepFM, DCN, NFM, FFM, AFM, DeepCrossing, WideDeep and DIN "
                                   "(PNN: PNN.train_step)")
     dev = torch.device(device) if device is not None else model._dev
     labels = torch.as_tensor(np.asarray(labels, np.float32), device=dev)
