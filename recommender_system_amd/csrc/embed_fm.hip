@@ -110,9 +110,10 @@ __global__ __launch_bounds__(NW * 64) void embed_fm_mfma(EmbedFmArgs a) {
 // the field metadata by value (rs_embed_fm_fwd_hm): each wave loads its own
 // fields' ids and reads (offset, vocab) through scalar kernarg loads — no LDS
 // id tile, no barrier, no per-wave metadata loads from one hot L2 line
-template <int KV, int NT, int NW, int KIND, bool PF, int FC = 0, int KFMC = 0, int NDC = -1>
+// (ID1: both passes' ids in one load — embed_fm_body.hpp; the single launch takes it for integer ids, KV * NT <= 8)
+template <int KV, int NT, int NW, int KIND, bool PF, int FC = 0, int KFMC = 0, int NDC = -1, bool ID1 = false>
 __global__ __launch_bounds__(NW * 64) void embed_fm_mfma_ka(EmbedFmArgs a, FieldMeta m) {
-  embed_fm_body<KV, NT, NW, KIND, false, 1, PF, true, FC, KFMC, NDC>(a, nullptr, blockIdx.x, &m);
+  embed_fm_body<KV, NT, NW, KIND, false, 1, PF, true, FC, KFMC, NDC, false, ID1>(a, nullptr, blockIdx.x, &m);
 }
 
 // ---- the kernarg kernels with their hot arguments preloaded (RS_OPT_EMBED_FM_KERNEL 5;
@@ -135,12 +136,12 @@ static int headline_spec(const EmbedFmArgs& a) {
   return ct_geom_matches<4, 1, 26, 10, 13>(a) ? 1 : -1;
 }
 
-template <int KV, int NT, int NW, int KIND, bool PF, int FC = 0, int KFMC = 0, int NDC = -1>
+template <int KV, int NT, int NW, int KIND, bool PF, int FC = 0, int KFMC = 0, int NDC = -1, bool ID1 = false>
 __global__ __launch_bounds__(NW * 64) void embed_fm_mfma_kp(const float* prep, const void* ids, int64_t id_stride,
                                                             int64_t batch, const float* dense, int64_t dense_stride,
                                                             const float* table, EmbedFmCold c, FieldMeta m) {
   const EmbedFmArgs a = hot_cold_args<KV, NT, FC, KFMC, NDC>(prep, ids, id_stride, batch, dense, dense_stride, table, c);
-  embed_fm_body<KV, NT, NW, KIND, false, 1, PF, true, FC, KFMC, NDC, true>(a, nullptr, blockIdx.x, &m);
+  embed_fm_body<KV, NT, NW, KIND, false, 1, PF, true, FC, KFMC, NDC, true, ID1>(a, nullptr, blockIdx.x, &m);
 }
 
 // S consecutive batches in ONE launch (rs_embed_fm_fwd_hm_stream): workgroup
@@ -292,16 +293,20 @@ static void launch_embed_fm3(const EmbedFmArgs& a, hipStream_t st, const FieldMe
         // mismatch would take the generic kernel, which reads the run-time one)
         if (headline_spec(a) == 1) {
           if (pl)
-            embed_fm_mfma_kp<KV, NT, 16, KIND, true, 26, 10, 13><<<grid, 16 * 64, 0, st>>>(
+            embed_fm_mfma_kp<KV, NT, 16, KIND, true, 26, 10, 13, true><<<grid, 16 * 64, 0, st>>>(
                 a.prep, a.ids, a.id_stride, a.batch, a.dense, a.dense_stride, a.table, c, *hm);
-          else embed_fm_mfma_ka<KV, NT, 16, KIND, true, 26, 10, 13><<<grid, 16 * 64, 0, st>>>(a, *hm);
+          else embed_fm_mfma_ka<KV, NT, 16, KIND, true, 26, 10, 13, true><<<grid, 16 * 64, 0, st>>>(a, *hm);
           return;
         }
       }
+      // (any other shape: the merged id load too — 5.55 -> 5.41 us at 26 fields, FM width 8 — for integer
+      // ids and where embed_fm_body runs its two-pass schedule, PRE: KV * NT <= 8.  Longer rows, k 64 or
+      // k 32 with two column tiles, take the pass-at-a-time loop, which loads each pass's ids on its own.)
+      constexpr bool ID1 = KIND != 2 && KV * NT <= 8;
       if (pl)
-        embed_fm_mfma_kp<KV, NT, 16, KIND, true><<<grid, 16 * 64, 0, st>>>(a.prep, a.ids, a.id_stride, a.batch, a.dense,
-                                                                           a.dense_stride, a.table, c, *hm);
-      else embed_fm_mfma_ka<KV, NT, 16, KIND, true><<<grid, 16 * 64, 0, st>>>(a, *hm);
+        embed_fm_mfma_kp<KV, NT, 16, KIND, true, 0, 0, -1, ID1><<<grid, 16 * 64, 0, st>>>(
+            a.prep, a.ids, a.id_stride, a.batch, a.dense, a.dense_stride, a.table, c, *hm);
+      else embed_fm_mfma_ka<KV, NT, 16, KIND, true, 0, 0, -1, ID1><<<grid, 16 * 64, 0, st>>>(a, *hm);
       return;
     }
   }

@@ -44,10 +44,16 @@ namespace rs {
 // constants (0 / 0 / -1: the kernel arguments' run-time values) — the
 // headline shape's kernarg and streamed kernels take 26 / 10 / 13
 // PL: the caller's hot arguments arrived preloaded in SGPRs (embed_fm_mfma_kp)
+// ID1: a wave with two passes loads both passes' ids with ONE instruction
+// (the kernarg kernels' single launch, integer ids, only with the two-pass
+// schedule PRE below, which splits the load: at one or two tiles per CU
+// every vector-memory instruction in front of the rows is on the critical
+// path)
 template <int KV, int NT, int NW, int KIND, bool TW, int MC = 0, bool PF = false, bool KA = false, int FC = 0,
-          int KFMC = 0, int NDC = -1, bool PL = false>
+          int KFMC = 0, int NDC = -1, bool PL = false, bool ID1 = false>
 __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArgs* tw, const int tile,
                                               const FieldMeta* km = nullptr) {
+  static_assert(!ID1 || (KA && PF && !TW && KIND < 2 && MC == 1), "ID1: the kernarg kernels' two-pass schedule only");
   const int aF = FC > 0 ? FC : a.F;        // (compile-time at the specialised shapes)
   const int akfm = KFMC > 0 ? KFMC : a.kfm;
   const int and_ = NDC >= 0 ? NDC : a.nd;
@@ -245,6 +251,9 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
   // Measured (scripts/ab, profiles/r3_ab_prefetch_*.json): 14.51 vs 15.30 us
   // at batch 16384 (4 tiles per CU), 6.15 vs 6.13 at 4096 (1 tile per CU)
   constexpr bool PRE = PF && KV * MAXC * NT <= 8;
+  // (the merged id load is split in the PRE block and nowhere else: the pass-at-a-time loop would decode
+  // the other field's id in half the lanes and a stale id in its second pass)
+  static_assert(!ID1 || PRE, "ID1 needs the two-pass schedule (PRE)");
   const int wv = threadIdx.x >> 6;
   // a pass's ids and field metadata (issue_rows takes them from here)
   auto fetch_ids = [&](int cg, Pass& P) {
@@ -267,7 +276,15 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
         } else if constexpr (KA) {  // kernarg metadata: scalar loads, wave-uniform field
           offc[j] = km->off[P.cj[j]];
           vocc[j] = km->voc[P.cj[j]];
-          P.rid[j] = I::load(a.ids, b * a.id_stride + P.cj[j]);
+          if constexpr (ID1) {
+            // one load serves both passes of a two-pass wave: k-slots 0 / 1
+            // take the first pass's field, k-slots 2 / 3 the second's (the
+            // same sample, 32 lanes apart); the halves change places in front
+            // of the first decode, below.  A one-pass wave loads as before.
+            if (cg == 0) P.rid[j] = I::load(a.ids, b * a.id_stride + P.cj[j] + (PS + w < aF && kk >= 2 ? PS : 0));
+          } else {
+            P.rid[j] = I::load(a.ids, b * a.id_stride + P.cj[j]);
+          }
         } else {
           const int cv = min(cg + j * NW + wv, aF - 1);
           offc[j] = a.offs[cv];
@@ -389,6 +406,23 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
     if (!coop && aF > 0) load_dense();
     late_args();
     if (one) {
+      if constexpr (ID1) {
+        // v_permlane32_swap hands each half of the wave the other half's id:
+        // every lane then holds the first pass's id in [0] and the second
+        // pass's in [1] — the values the two loads put there (a one-pass wave
+        // loaded its field in both halves: [0] is unchanged, [1] unused)
+        if constexpr (sizeof(typename I::raw_t) == 4) {
+          const auto h = __builtin_amdgcn_permlane32_swap((unsigned)P0.rid[0], (unsigned)P0.rid[0], false, false);
+          P0.rid[0] = (int32_t)h[0];
+          P1.rid[0] = (int32_t)h[1];
+        } else {
+          const uint64_t r = (uint64_t)P0.rid[0];
+          const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)r, (unsigned)r, false, false);
+          const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(r >> 32), (unsigned)(r >> 32), false, false);
+          P0.rid[0] = (int64_t)((uint64_t)hi[0] << 32 | lo[0]);
+          P1.rid[0] = (int64_t)((uint64_t)hi[1] << 32 | lo[1]);
+        }
+      }
       issue_rows(0, P0, true);
       // (PL: w0, requested in late_args, is taken here, under the row trip —
       // left alone its load sinks behind the MFMAs, a dependent trip at the end)

@@ -29,7 +29,8 @@ def main():
     dev = torch.device("cuda")
     names = [n for n in "ABCD" if os.path.exists(os.path.join(ROOT, "scripts", "ab", f"librs_ab_{n}.so"))]
     libs = {n: bind(os.path.join(ROOT, "scripts", "ab", f"librs_ab_{n}.so")) for n in names}
-    F, k, kfm, nd = 26, 16, 10, 13
+    # DIAG_KFM other than 10 leaves the specialised shape: the generic kernarg kernels run
+    F, k, kfm, nd = 26, 16, int(os.environ.get("DIAG_KFM", "10")), 13
     V = int(float(os.environ.get("DIAG_V", "1e7")))
     B = int(os.environ.get("DIAG_B", "4096"))
     table = torch.empty(F * V, k, device=dev).uniform_(-0.05, 0.05)

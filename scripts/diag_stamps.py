@@ -5,8 +5,8 @@ s_memrealtime stamps, 100 MHz, scripts/build_diag.sh): per workgroup / wave
   pass's rows issued, in front of the first pass's MFMAs), t3 wave's MFMAs
   done (dense included), t7 combine barrier released, t4 end (wave 0).
 RS_DIAG_HM=1 runs the kernarg-metadata kernel (rs_embed_fm_fwd_hm's), DIAG_OPT
-sets RS_OPT_EMBED_FM_KERNEL.  Prints percentiles (us) relative to the
-earliest t0 of the launch."""
+sets RS_OPT_EMBED_FM_KERNEL, DIAG_LIB names another stamped build to load.
+Prints percentiles (us) relative to the earliest t0 of the launch."""
 import ctypes as C
 import json
 import os
@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 
 
 def main():
-    lib = C.CDLL(os.path.join(ROOT, "recommender_system_amd", "librs_hip_diag.so"))
+    lib = C.CDLL(os.environ.get("DIAG_LIB") or os.path.join(ROOT, "recommender_system_amd", "librs_hip_diag.so"))
     P, L, I = C.c_void_p, C.c_int64, C.c_int
     lib.rs_diag_embed_fm_fwd.argtypes = [P, I, L, P, L, I, P, P, P, I, I, P, P, I, P, L, P, P]
     lib.rs_fm_prepare.argtypes = [P, P, I, I, I, I, P, P]
@@ -65,6 +65,7 @@ def main():
            "start (t0)": pct(t[:, :, 0] - base),
            "kernarg (t5-t0)": pct(t[:, :, 5] - t[:, :, 0]),
            "p0 ids decoded (t1 - t0)": pct(t[:, :, 1] - t[:, :, 0]),
+           "p0 rest of the id wait + decode (t1 - t6)": pct(t[:, :, 1] - t[:, :, 6]),
            "p0 rows arrived (t2 - t1)": pct(t[:, :, 2] - t[:, :, 1]),
            "p0 mfma (t13 - t2)": pct(t[:, :, 13] - t[:, :, 2]),
            "p1 ids decoded (t11 - t0)": pct(t[:, w2, 11] - t[:, w2, 0]),
@@ -75,7 +76,10 @@ def main():
            "p1 mfma (t14 - t12)": pct(t[:, w2, 14] - t[:, w2, 12]),
            "wave done (t3) 2-field waves": pct(t[:, w2, 3] - base),
            "wave done (t3) 1-field waves": pct(t[:, w1, 3] - base),
+           "last MFMA to wave done (t3 - t14) 2-field waves": pct(t[:, w2, 3] - t[:, w2, 14]),
+           "last field MFMA to wave done (t3 - t13) 1-field waves": pct(t[:, w1, 3] - t[:, w1, 13]),
            "slowest wave t3 in WG": pct(np.nanmax(t[:, :, 3], 1) - base),
+           "slowest wave done to barrier released (t7 - max t3)": pct(t[:, 0, 7] - np.nanmax(t[:, :, 3], 1)),
            "barrier released (t7)": pct(t[:, 0, 7] - base),
            "combine (t4 - t7, wave 0)": pct(t[:, 0, 4] - t[:, 0, 7]),
            "end (t4)": pct(t[:, 0, 4] - base),
