@@ -789,6 +789,130 @@ int rs_mmoe_fwd(const float* x, int64_t x_stride, int d, int hidden,
                 float* y, int64_t y_task_stride, int64_t y_stride,
                 int64_t batch, rs_stream_t stream);
 
+/* ------------------------------- DIEN interest evolution (a19), forward
+ * model/dien.py:54-70 on a behaviour sequence keys [B, T, D], a candidate q
+ * [B, D] and lengths len [B] (int32 or int64; position t is valid iff t <
+ * len[b]: a length >= T makes every position valid, <= 0 none), in ONE launch
+ * over 16-sample tiles:
+ *   gru1 (Keras GRU, reset_after=True, gate order z r h; kernel W [D, 3 D],
+ *   recurrent_kernel U [D, 3 D], bias [2, 3 D] = input row, recurrent row):
+ *     xi = x_t W + bias[0]            hr = h U + bias[1]
+ *     z = sig(xi_z + hr_z)  r = sig(xi_r + hr_r)  hh = tanh(xi_h + r * hr_h)
+ *     h <- z * h + (1 - z) * hh       h_0 = 0, H1[b, t] = h
+ *   scores (AttentionSequencePoolingLayer(return_score=True),
+ *   layer/sequence.py:237-273, over LocalActivationUnit, layer/core.py:94-108):
+ *     e_t = [q, H1_t, q - H1_t, q * H1_t]                       (4 D wide)
+ *     y = act(act(e_t W_0 + b_0) W_1 + b_1)     s[b, t] = y . w_out + b_out
+ *     weight_norm: s = -2^32 + 1 at t >= len, then softmax over T (the row
+ *     maximum subtracted); else s = 0 at t >= len, no softmax
+ *     att_act: RS_ACT_RELU, RS_ACT_SIGMOID or RS_ACT_DICE (inference Dice,
+ *     layer/activation.py:32-66: p = sig((x - mean) / sqrt(var + 1e-9)),
+ *     y = alpha * (1 - p) * x + p * x, per unit)
+ *   gru2 (AUGRU over AUGRUCell, layer/sequence.py:293-395, layer/activation.py:
+ *   91-142; no bias; hsig(x) = clip(0.2 x + 0.5, 0, 1); a = s[b, t]):
+ *     z = a * hsig(x W_z + h U_z)     r = hsig(x W_r + h U_r)
+ *     hh = tanh(x W_h + (r * h) U_h)
+ *     h <- z * h + (1 - z) * hh       (augru_update 0, the reference)
+ *     h <- (1 - z) * h + z * hh       (augru_update 1, the DIEN paper)
+ *     x = H1_t, h_0 = 0, hist[b] = h after step T - 1
+ * Both recurrences run all T steps, padded positions included (no Keras mask
+ * reaches them: dien.py:116-117 builds the embeddings with
+ * seq_mask_zero=False).
+ * Layer 1 of the attention MLP is regrouped per sample as q (Wq + Wd) + b_0 +
+ * H1_t (Wk - Wd) + (q * H1_t) Wp with W_0 = [Wq; Wk; Wd; Wp] (D rows each),
+ * so its sums are ordered differently from e_t W_0 (fp32 rounding only).
+ * A sample's results do not depend on the batch, its tile mates or the
+ * optional outputs: hist is bit-identical with and without H1 / scores, for
+ * any split of the batch, and between the dense and the ids form.
+ * Caps of the one-launch form (rs_dien_evolution_ok: 1 when it takes the
+ * shape): 1 <= D <= 64; exactly two attention layers, each 1..128 wide;
+ * att_act one of the three; and, with Dp = roundup(D, 16), the tile's LDS
+ *   4 * (16 * T * Dp + 32 * Dp + 16 * T) <= 160 KiB
+ * (the sequence tile that becomes H1, the state and r * h tiles, the scores) —
+ * T <= 50 at D 36, T <= 148 at D <= 16.  A refused shape runs unfused in the
+ * host layer (rs_gru_fwd, the scores from older entries / torch,
+ * rs_augru_fwd).  H1 is not spilled to a global workspace for larger T: the
+ * unfused path already keeps H1 in HBM, and a third variant would only
+ * duplicate it.
+ * prepared (rs_dien_prepared_size floats, -1 on a bad shape; independent of
+ * T), with A1p / A2p = roundup(att_hidden[0] / [1], 16):
+ *   2 * (6 * Dp * Dp + 6 * Dp)                       the two gru images
+ *   + 3 * A1p * Dp + 4 * A1p + A2p * A1p + 5 * A2p + 4   the attention image
+ * gru image (rs_gru_prepared_size(din, units) = 3 * Up * Kp + 3 * Up * Up +
+ * 6 * Up floats, Kp / Up = roundup(din / units, 16); din, units <= 64): [W | U
+ * | bias [2][3][Up]], a matrix as 3 gates x Up / 16 column tiles x k-groups of
+ * MFMA fragments (lane l, element j: M[16 g + 4 (l >> 4) + j][gate * units +
+ * 16 c + (l & 15)]); attention image: [Wk - Wd | Wp | Wq + Wd | b_0 | dice_0
+ * (mean, 1 / sqrt(var + 1e-9), alpha) | W_1 | b_1 | dice_1 | w_out | b_out
+ * (4)], matrices in the same fragment order.  Padding is zeros.
+ * rs_dien_prepare: att_W / att_b / dice_*: host arrays of n_att_layers device
+ * pointers (Keras kernels [in, out]; dice_* read for RS_ACT_DICE only, else
+ * may be NULL); gru1_bias [2, 3 D]; att_out_w [att_hidden[1]], att_out_b [1].
+ * rs_gru_prepare: bias NULL = zeros (the AUGRU has none).
+ * rs_dien_evolution_fwd: keys[b, t, :] at keys + b * keys_bstride + t *
+ * keys_tstride; optional H1 [B, T, D] and scores [B, T] (contiguous); hist
+ * [B, D], rows hist_stride apart.
+ * rs_dien_evolution_ids_fwd: 1..4 behaviour features concatenated along D
+ * (widths add up to D): feature f's history ids hist_ids[f] [B, T] (rows
+ * hist_strides[f] elements apart), candidate ids cand_ids[f] [B] (cand_strides
+ * [f] apart), both of kinds[f] (RS_ID_*), looked up in tables[f] [vocabs[f],
+ * widths[f]].  An id outside [0, vocab) reads a zero row and sets *err_flag.
+ * The [B, T, D] keys are never written to HBM.
+ * rs_gru_fwd (x [B, T, din] -> seq [B, T, units] and / or last [B, units]) and
+ * rs_augru_fwd (x, scores [B, T] -> last) are the same device functions as
+ * stand-alone launches, reading x step by step from global memory; din may
+ * differ from units.
+ * Stream-ordered, graph-capturable; arguments are validated before any device
+ * work; nothing is launched for batch 0.                                     */
+#define RS_ACT_DICE 4 /* rs_dien_* only */
+int rs_dien_evolution_ok(int T, int D, int n_att_layers, const int* att_hidden,
+                         int att_act);
+int64_t rs_dien_prepared_size(int D, int n_att_layers, const int* att_hidden);
+int rs_dien_prepare(int D, const float* gru1_kernel,
+                    const float* gru1_recurrent, const float* gru1_bias,
+                    const float* gru2_kernel, const float* gru2_recurrent,
+                    int n_att_layers, const int* att_hidden, int att_act,
+                    const float* const* att_W, const float* const* att_b,
+                    const float* const* dice_mean,
+                    const float* const* dice_var,
+                    const float* const* dice_alpha, const float* att_out_w,
+                    const float* att_out_b, float* prepared,
+                    rs_stream_t stream);
+int rs_dien_evolution_fwd(const float* keys, int64_t keys_bstride,
+                          int64_t keys_tstride, const float* q,
+                          int64_t q_stride, const void* len, int len_kind,
+                          int T, int D, int n_att_layers,
+                          const int* att_hidden, int att_act, int weight_norm,
+                          int augru_update, const float* prepared, float* H1,
+                          float* scores, float* hist, int64_t hist_stride,
+                          int64_t batch, rs_stream_t stream);
+int rs_dien_evolution_ids_fwd(int n_feat, const int* widths, const int* kinds,
+                              const void* const* hist_ids,
+                              const int64_t* hist_strides,
+                              const void* const* cand_ids,
+                              const int64_t* cand_strides,
+                              const float* const* tables,
+                              const int64_t* vocabs, const void* len,
+                              int len_kind, int T, int D, int n_att_layers,
+                              const int* att_hidden, int att_act,
+                              int weight_norm, int augru_update,
+                              const float* prepared, float* H1, float* scores,
+                              float* hist, int64_t hist_stride, int64_t batch,
+                              int* err_flag, rs_stream_t stream);
+int64_t rs_gru_prepared_size(int din, int units);
+int rs_gru_prepare(int din, int units, const float* kernel,
+                   const float* recurrent, const float* bias, float* prepared,
+                   rs_stream_t stream);
+int rs_gru_fwd(const float* x, int64_t x_bstride, int64_t x_tstride, int T,
+               int din, int units, const float* prepared, float* seq,
+               float* last, int64_t last_stride, int64_t batch,
+               rs_stream_t stream);
+int rs_augru_fwd(const float* x, int64_t x_bstride, int64_t x_tstride,
+                 const float* scores, int64_t scores_stride, int T, int din,
+                 int units, int augru_update, const float* prepared,
+                 float* last, int64_t last_stride, int64_t batch,
+                 rs_stream_t stream);
+
 /* ------------------------------------------ wide part of Wide&Deep (a17)
  * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
  * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense

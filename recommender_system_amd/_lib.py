@@ -103,6 +103,15 @@ SIGNATURES = {
     "rs_mmoe_prepared_size": (L, [I, I, I, I, I, P]),
     "rs_mmoe_prepare": (I, [I, I, I, I, P, P, P, P, I, P, P, P, P, P]),
     "rs_mmoe_fwd": (I, [P, L, I, I, I, I, I, P, P, P, P, L, P, L, L, L, P]),
+    "rs_dien_evolution_ok": (I, [I, I, I, P, I]),
+    "rs_dien_prepared_size": (L, [I, I, P]),
+    "rs_dien_prepare": (I, [I, P, P, P, P, P, I, P, I, P, P, P, P, P, P, P, P, P]),
+    "rs_dien_evolution_fwd": (I, [P, L, L, P, L, P, I, I, I, I, P, I, I, I, P, P, P, P, L, L, P]),
+    "rs_dien_evolution_ids_fwd": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, I, I, P, P, P, P, L, L, P, P]),
+    "rs_gru_prepared_size": (L, [I, I]),
+    "rs_gru_prepare": (I, [I, I, P, P, P, P, P]),
+    "rs_gru_fwd": (I, [P, L, L, I, I, I, P, P, P, L, L, P]),
+    "rs_augru_fwd": (I, [P, L, L, P, L, I, I, I, I, P, P, L, L, P]),
     "rs_wide_onehot_fwd":(I, [P, I, L, P, L, I, P, P, I, P, P, P, L, P, P]),
     "rs_concat_pieces": (I, [I, P, P, P, P, P, P, P, P, L, L, P, P]),
     "rs_deepfm_fused_ok": (I, [I, I, I, I, I, P]),

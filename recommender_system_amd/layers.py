@@ -19,6 +19,15 @@ Each class keeps the reference layer's name, constructor arguments and
              use_gate_bias)                   layer/interaction.py:429-509
   tower_layer(hidden_units, output_dim, activation='relu')
                                               layer/interaction.py:512-523
+  GRU(units, return_sequences)                Keras GRU as model/dien.py:65 uses it
+  AUGRU(units, gru_type) / AUGRUCell(units)   layer/sequence.py:293-395, layer/activation.py:91-142
+  LocalActivationUnit(hidden_units, activation)
+                                              layer/core.py:55-108
+  AttentionSequencePoolingLayer(att_hidden_units, att_activation,
+      weight_normalization, return_score)     layer/sequence.py:205-273
+  DNN(hidden_units, activation, use_bn, ...)  layer/core.py:123-205
+  PredictionLayer(task, use_bias)             layer/core.py:223-256
+  InterestEvolution(embedding_size, ...)      model/dien.py:54-80 (interest_evolution)
   Dense / PReLU / BatchNormalization          the Keras layers the models use
 
 Weights are built lazily on the first call from the input shape, like Keras
@@ -1546,4 +1555,582 @@ class WideLayer(KerasModule):
              ptr(err.t), _stream())
         if check_ids:
             err.check("WideLayer")
+        return out
+
+
+# ------------------------------------------------- DIEN: sequence layers
+_DIEN_ACTS = {"relu": 1, "sigmoid": 3, "dice": 4}  # RS_ACT_RELU, RS_ACT_SIGMOID, RS_ACT_DICE
+_DIEN_UPDATES = {"reference": 0, "paper": 1}
+_RNN_MAXW = 64  # dien.hip: input width and units of rs_gru_fwd / rs_augru_fwd, D of the fused launch
+
+
+def _glorot_normal(fan_in, fan_out, gen, device):
+    """Keras glorot_normal: a normal truncated at two standard deviations,
+    scaled so that the truncated variable has variance 2 / (fan_in + fan_out)."""
+    std = math.sqrt(2.0 / (fan_in + fan_out)) / 0.87962566103423978
+    t = torch.randn(fan_in, fan_out, generator=gen, device="cpu")
+    for _ in range(64):
+        far = t.abs() > 2
+        if not bool(far.any()):
+            break
+        t[far] = torch.randn(int(far.sum()), generator=gen, device="cpu")
+    return t.clamp_(-2, 2).mul_(std).to(device)
+
+
+def _orthogonal(rows, cols, gen, device):
+    """Keras Orthogonal(gain=1): Q of the QR of a normal matrix, signs fixed by diag(R)."""
+    a = torch.randn(max(rows, cols), min(rows, cols), generator=gen, device="cpu", dtype=torch.float64)
+    q, r = torch.linalg.qr(a)
+    q = q * torch.sign(torch.diagonal(r))
+    if rows < cols:
+        q = q.t()
+    return q.to(torch.float32).contiguous().to(device)
+
+
+def _seq_input(x, device, what):
+    x = x if (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32) else _to_device_f32(x, device)
+    if x.dim() != 3:
+        raise ValueError(f"{what}: expected [batch, T, width], got shape {tuple(x.shape)}")
+    return x if x.stride(2) == 1 else x.contiguous()
+
+
+def _lengths(seq_length, device, B):
+    t = torch.as_tensor(seq_length)
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.to(torch.int64)
+    t = t.reshape(-1).to(device).contiguous()
+    if t.numel() != B:
+        raise ValueError(f"seq_length holds {t.numel()} lengths for a batch of {B}")
+    return t
+
+
+class _Recurrent(KerasModule):
+    """kernel [din, 3 units] and recurrent_kernel [units, 3 units], gate order
+    z r h, and their packed image (rs_gru_prepare), cached per weight version."""
+
+    use_bias = False
+
+    def __init__(self, units, device=None, seed=None, input_dim=None):
+        super().__init__(device, seed)
+        self.units = int(units)
+        if self.units < 1:
+            raise ValueError("units must be >= 1")
+        self.kernel = self.recurrent_kernel = self.bias = None
+        if input_dim is not None:
+            self.build(input_dim)
+
+    @property
+    def built(self):
+        return self.kernel is not None
+
+    def _recurrent_init(self):
+        u = self.units
+        return _glorot_uniform(u, 3 * u, self._gen, self._dev)
+
+    def build(self, din):
+        din, u = int(din), self.units
+        if max(din, u) > _RNN_MAXW:
+            raise NotImplementedError(f"{type(self).__name__}: input width and units up to {_RNN_MAXW} "
+                                      f"(got {din}, {u})")
+        self.input_dim = din
+        self.kernel = nn.Parameter(_glorot_uniform(din, 3 * u, self._gen, self._dev), requires_grad=False)
+        self.recurrent_kernel = nn.Parameter(self._recurrent_init(), requires_grad=False)
+        if self.use_bias:
+            self.bias = nn.Parameter(torch.zeros(2, 3 * u, device=self._dev), requires_grad=False)
+        self._invalidate()
+
+    def keras_weights(self):
+        if not self.built:
+            raise RuntimeError(f"{type(self).__name__}: not built (call build(input_dim) or run a forward first)")
+        return super().keras_weights()
+
+    def _invalidate(self):
+        self.__dict__.pop("_rnn_prep", None)
+
+    def prepared(self):
+        ps = [p for p in (self.kernel, self.recurrent_kernel, self.bias) if p is not None]
+        key = tuple((p._version, p.data_ptr()) for p in ps)
+        ent = self.__dict__.get("_rnn_prep")
+        if ent is None or ent[0] != key:
+            size = _lib.lib().rs_gru_prepared_size(self.input_dim, self.units)
+            if size < 0:
+                _lib.check(-1, "rs_gru_prepared_size")
+            prep = torch.empty(size, dtype=torch.float32, device=self._dev)
+            call("rs_gru_prepare", self.input_dim, self.units, ptr(self.kernel), ptr(self.recurrent_kernel),
+                 ptr(self.bias), ptr(prep), _stream())
+            ent = self.__dict__["_rnn_prep"] = (key, prep)
+        return ent[1]
+
+    def _input(self, inputs):
+        x = _seq_input(inputs, self._dev, type(self).__name__)
+        if not self.built:
+            self.build(x.shape[2])
+        if x.shape[2] != self.input_dim:
+            raise ValueError(f"{type(self).__name__} built for {self.input_dim} inputs, got {x.shape[2]}")
+        return x
+
+
+class GRU(_Recurrent):
+    """GRU(units, return_sequences=False) — the subset of Keras GRU that DIEN
+    uses (model/dien.py:65): TF2 defaults reset_after=True, use_bias=True, tanh /
+    sigmoid, gate order z r h, zero initial state, no mask.  Weights: ``kernel``
+    [din, 3 units] glorot-uniform, ``recurrent_kernel`` [units, 3 units]
+    orthogonal, ``bias`` [2, 3 units] zeros (input row, recurrent row).
+    ``forward(x[B, T, din])`` is one rs_gru_fwd launch (dien.hip): [B, T, units]
+    with return_sequences, else the last state [B, units]."""
+
+    use_bias = True
+
+    def __init__(self, units, return_sequences=False, device=None, seed=None, input_dim=None):
+        super().__init__(units, device, seed, input_dim)
+        self.return_sequences = bool(return_sequences)
+
+    def _recurrent_init(self):
+        return _orthogonal(self.units, 3 * self.units, self._gen, self._dev)
+
+    def forward(self, inputs):
+        x = self._input(inputs)
+        B, T, _ = x.shape
+        u = self.units
+        if T < 1:
+            raise ValueError("GRU: an empty sequence")
+        if self.return_sequences:
+            seq = torch.empty(B, T, u, dtype=torch.float32, device=self._dev)
+            call("rs_gru_fwd", ptr(x), x.stride(0), x.stride(1), T, self.input_dim, u, ptr(self.prepared()), ptr(seq),
+                 None, 0, B, _stream())
+            return seq
+        last = torch.empty(B, u, dtype=torch.float32, device=self._dev)
+        call("rs_gru_fwd", ptr(x), x.stride(0), x.stride(1), T, self.input_dim, u, ptr(self.prepared()), None,
+             ptr(last), last.stride(0), B, _stream())
+        return last
+
+
+class AUGRUCell(_Recurrent):
+    """AUGRUCell(units) — layer/activation.py:91-142: the weights of the
+    attention-update GRU, ``kernel`` [din, 3 units] and ``recurrent_kernel``
+    [units, 3 units] (add_weight's default glorot-uniform, no bias)."""
+
+
+class AUGRU(KerasModule):
+    """AUGRU(units, gru_type='AUGRU', return_sequences=False) —
+    layer/sequence.py:293-395 over AUGRUCell: z = a hsig(x W_z + h U_z),
+    r = hsig(x W_r + h U_r), hh = tanh(x W_h + (r h) U_h), h <- z h + (1 - z) hh
+    with hsig = clip(0.2 x + 0.5, 0, 1) and a the attention score of the step.
+    ``forward(x[B, T, din], att_score[B, T])`` returns the last state [B, units]
+    (one rs_augru_fwd launch).  ``gru_type`` is accepted and ignored, as in the
+    reference (its __init__ never passes it to the cell).  ``augru_update=
+    'paper'`` swaps the blend to the DIEN paper's h <- (1 - z) h + z hh."""
+
+    def __init__(self, units, gru_type="AUGRU", return_sequences=False, augru_update="reference", device=None,
+                 seed=None, input_dim=None):
+        super().__init__(device, seed)
+        if return_sequences:
+            raise NotImplementedError("AUGRU: return_sequences=True is not built (DIEN uses the last state)")
+        if augru_update not in _DIEN_UPDATES:
+            raise ValueError(f"augru_update must be 'reference' or 'paper', got {augru_update!r}")
+        self.gru_type, self.augru_update = gru_type, augru_update
+        self.cell = AUGRUCell(units, device=device, seed=_subseed(self._gen), input_dim=input_dim)
+
+    @property
+    def units(self):
+        return self.cell.units
+
+    def keras_weights(self):
+        return self.cell.keras_weights()
+
+    def set_keras_weights(self, weights, strict=True):
+        self.cell.set_keras_weights(weights, strict)
+
+    def forward(self, inputs, att_score):
+        c = self.cell
+        x = c._input(inputs)
+        B, T, _ = x.shape
+        a = att_score if (torch.is_tensor(att_score) and att_score.is_cuda) else _to_device_f32(att_score, self._dev)
+        a = a.reshape(B, T).to(torch.float32).contiguous()
+        last = torch.empty(B, c.units, dtype=torch.float32, device=self._dev)
+        call("rs_augru_fwd", ptr(x), x.stride(0), x.stride(1), ptr(a), a.stride(0), T, c.input_dim, c.units,
+             _DIEN_UPDATES[self.augru_update], ptr(c.prepared()), ptr(last), last.stride(0), B, _stream())
+        return last
+
+
+class DNN(KerasModule):
+    """DNN(hidden_units, activation='relu', l2_reg=0, dropout_rate=0,
+    use_bn=False, output_activation=None) — layer/core.py:123-205 (the
+    DeepCTR-style tower; DNNLayer is the reference's other one): per layer
+    Dense with bias, BatchNormalization when use_bn, the activation ('relu',
+    'sigmoid', 'dice', 'prelu', 'linear' / None) — the last layer included —
+    and an inference-inactive Dropout.  Weights ``kernel{i}`` glorot-normal,
+    ``bias{i}`` zeros, ``bn{i}/…``, ``dice{i}/…``, ``alpha{i}``.  The input's
+    last axis is contracted; leading axes are kept.  Each layer is rs_dense_fwd
+    (+ rs_affine_act for BN, rs_dice_fwd for Dice); the models fuse a BN-free
+    relu / sigmoid tower into one rs_mlp_fwd launch."""
+
+    def __init__(self, hidden_units, activation="relu", l2_reg=0, dropout_rate=0, use_bn=False,
+                 output_activation=None, device=None, seed=None, input_dim=None):
+        super().__init__(device, seed)
+        self.hidden_units = [int(u) for u in hidden_units]
+        acts = [activation] * len(self.hidden_units)
+        if output_activation and acts:
+            acts[-1] = output_activation
+        for a in acts:
+            if a not in _ACTS:
+                raise ValueError(f"unsupported activation {a!r}")
+        self.activation, self.output_activation, self.use_bn = activation, output_activation, bool(use_bn)
+        self.l2_reg, self.dropout_rate = l2_reg, dropout_rate
+        self.layers = nn.ModuleList([Dense(u, activation=a, device=device, seed=_subseed(self._gen))
+                                     for u, a in zip(self.hidden_units, acts)])
+        self.bn_layers = nn.ModuleList([BatchNormalization(device=device) for _ in self.hidden_units]) \
+            if self.use_bn else None
+        if input_dim is not None:
+            self.build(input_dim)
+
+    @property
+    def built(self):
+        return not self.layers or self.layers[0].kernel is not None
+
+    def build(self, n):
+        for i, l in enumerate(self.layers):
+            l.build(n)
+            with torch.no_grad():
+                l.kernel.copy_(_glorot_normal(n, l.units, self._gen, self._dev))
+            if self.use_bn:
+                self.bn_layers[i].build(l.units)
+            n = l.units
+
+    def keras_weights(self):
+        if not self.built:
+            raise RuntimeError("DNN: not built (call build(input_dim) or run a forward first)")
+        out = {}
+        for i, l in enumerate(self.layers):
+            out[f"kernel{i}"], out[f"bias{i}"] = l.kernel, l.bias
+            if l.alpha is not None:
+                out[f"alpha{i}"] = l.alpha
+            if l.dice is not None:
+                out.update({f"dice{i}/{k}": v for k, v in l.dice.keras_weights().items()})
+            if self.use_bn:
+                out.update({f"bn{i}/{k}": v for k, v in self.bn_layers[i].keras_weights().items()})
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        own = self.keras_weights()
+        if strict and set(own) != set(weights):
+            raise KeyError(f"DNN: expected weights {sorted(own)}, got {sorted(weights)}")
+        with torch.no_grad():
+            for name, p in own.items():
+                if name in weights:
+                    p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
+        self._weights_changed()
+
+    def forward(self, inputs):
+        x = inputs if (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32) \
+            else _to_device_f32(inputs, self._dev)
+        if not self.built:
+            self.build(x.shape[-1])
+        lead = x.shape[:-1]
+        x = x.reshape(-1, x.shape[-1])
+        for i, l in enumerate(self.layers):
+            M, K = x.shape
+            if not self.use_bn:
+                x = l(x)  # Dense: rs_dense_fwd with the activation (Dice after it)
+                continue
+            y = torch.empty(M, l.units, dtype=torch.float32, device=self._dev)
+            call("rs_dense_fwd", ptr(x), x.stride(0), ptr(l.kernel), ptr(l.bias), None, 0, ptr(y), y.stride(0), M, K,
+                 l.units, _stream())
+            inv, shift = self.bn_layers[i].affine()
+            act = 0 if l.activation == "dice" else _lib.ACT[l.activation]
+            call("rs_affine_act", ptr(y), y.stride(0), ptr(inv), ptr(shift), ptr(l.alpha), act, ptr(y), y.stride(0), M,
+                 l.units, _stream())
+            x = l.dice(y, out=y) if l.activation == "dice" else y
+        return x.reshape(*lead, x.shape[-1])
+
+
+class LocalActivationUnit(KerasModule):
+    """LocalActivationUnit(hidden_units=(64, 32), activation='sigmoid') —
+    layer/core.py:55-108: [q, k, q - k, q * k] through DNN(hidden_units,
+    activation), then ``kernel`` [last, 1] (glorot-normal) and ``bias`` [1]:
+    ``forward([query[B, 1, D], keys[B, T, D]])`` returns [B, T, 1].  This is the
+    composed form (rs_dense_fwd per layer); DIEN's fused launch takes its
+    weights (dien.hip)."""
+
+    def __init__(self, hidden_units=(64, 32), activation="sigmoid", l2_reg=0, dropout_rate=0, use_bn=False,
+                 device=None, seed=None, input_dim=None):
+        super().__init__(device, seed)
+        self.hidden_units, self.activation = [int(u) for u in hidden_units], activation
+        self.dnn = DNN(self.hidden_units, activation, l2_reg, dropout_rate, use_bn, device=device,
+                       seed=_subseed(self._gen))
+        self.kernel = self.bias = None
+        if input_dim is not None:
+            self.build(input_dim)
+
+    @property
+    def built(self):
+        return self.kernel is not None
+
+    def build(self, D):
+        D = int(D)
+        self.embedding_size = D
+        self.dnn.build(4 * D)
+        size = 4 * D if not self.hidden_units else self.hidden_units[-1]
+        self.kernel = nn.Parameter(_glorot_normal(size, 1, self._gen, self._dev), requires_grad=False)
+        self.bias = nn.Parameter(torch.zeros(1, device=self._dev), requires_grad=False)
+
+    def keras_weights(self):
+        if not self.built:
+            raise RuntimeError("LocalActivationUnit: not built (call build(D) or run a forward first)")
+        out = {"kernel": self.kernel, "bias": self.bias}
+        out.update({f"dnn/{k}": v for k, v in self.dnn.keras_weights().items()})
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        own = self.keras_weights()
+        if strict and set(own) != set(weights):
+            raise KeyError(f"LocalActivationUnit: expected weights {sorted(own)}, got {sorted(weights)}")
+        with torch.no_grad():
+            for name, p in own.items():
+                if name in weights:
+                    p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
+        self._weights_changed()
+
+    def forward(self, inputs):
+        query, keys = inputs
+        keys = _seq_input(keys, self._dev, "LocalActivationUnit")
+        B, T, D = keys.shape
+        q = query if (torch.is_tensor(query) and query.is_cuda) else _to_device_f32(query, self._dev)
+        q = q.reshape(B, 1, D).to(torch.float32)
+        if not self.built:
+            self.build(D)
+        if D != self.embedding_size:
+            raise ValueError(f"LocalActivationUnit built for width {self.embedding_size}, got {D}")
+        qq = q.expand(B, T, D)
+        e = torch.cat([qq, keys, qq - keys, qq * keys], dim=-1).reshape(B * T, 4 * D)
+        y = self.dnn(e)
+        s = torch.empty(B * T, 1, dtype=torch.float32, device=self._dev)
+        if B * T:
+            call("rs_dense_fwd", ptr(y), y.stride(0), ptr(self.kernel), ptr(self.bias), None, 0, ptr(s), 1, B * T,
+                 y.shape[1], 1, _stream())
+        return s.reshape(B, T, 1)
+
+
+class AttentionSequencePoolingLayer(KerasModule):
+    """AttentionSequencePoolingLayer(att_hidden_units=(80, 40),
+    att_activation='sigmoid', weight_normalization=False, return_score=False)
+    — layer/sequence.py:205-273: ``forward([query[B, 1, D], keys[B, T, D],
+    keys_length[B, 1]])``: the LocalActivationUnit's scores, positions t >=
+    length set to -2**32 + 1 and a softmax over T (weight_normalization) or
+    set to 0 (none); returns the scores [B, 1, T] with return_score, else the
+    pooled keys scores @ keys [B, 1, D].  (The reference subscripts the method
+    ``as_list`` at :248; built as ``as_list()[1]``.)"""
+
+    def __init__(self, att_hidden_units=(80, 40), att_activation="sigmoid", weight_normalization=False,
+                 return_score=False, device=None, seed=None, input_dim=None):
+        super().__init__(device, seed)
+        self.att_hidden_units = [int(u) for u in att_hidden_units]
+        self.att_activation = att_activation
+        self.weight_normalization, self.return_score = bool(weight_normalization), bool(return_score)
+        self.local_att = LocalActivationUnit(self.att_hidden_units, att_activation, device=device,
+                                             seed=_subseed(self._gen), input_dim=input_dim)
+
+    def keras_weights(self):
+        return {f"local_att/{k}": v for k, v in self.local_att.keras_weights().items()}
+
+    def set_keras_weights(self, weights, strict=True):
+        self.local_att.set_keras_weights({k.split("/", 1)[1]: v for k, v in weights.items()
+                                          if k.startswith("local_att/")}, strict)
+
+    def forward(self, inputs):
+        query, keys, keys_length = inputs
+        keys = _seq_input(keys, self._dev, "AttentionSequencePoolingLayer")
+        B, T, _ = keys.shape
+        s = self.local_att([query, keys]).reshape(B, T)
+        L = _lengths(keys_length, self._dev, B)
+        valid = torch.arange(T, device=self._dev).unsqueeze(0) < L.unsqueeze(1)
+        if self.weight_normalization:
+            s = torch.softmax(torch.where(valid, s, torch.full_like(s, float(-2 ** 32 + 1))), dim=-1)
+        else:
+            s = torch.where(valid, s, torch.zeros_like(s))
+        s = s.unsqueeze(1)
+        return s if self.return_score else torch.matmul(s, keys)
+
+
+class InterestEvolution(KerasModule):
+    """interest_evolution(...) of model/dien.py:54-80 as a module: ``gru1`` =
+    GRU(D, return_sequences=True), ``attention`` = AttentionSequencePoolingLayer(
+    att_hidden_units, att_activation, weight_normalization, return_score=True)
+    and ``gru2`` = AUGRU(D), on keys [B, T, D], a query [B, D] and lengths [B].
+
+    ``forward(keys, query, seq_length)`` returns hist [B, D].  It is ONE
+    rs_dien_evolution_fwd launch (dien.hip: H1 and the scores stay in LDS) when
+    ``fused_ok(T)``; otherwise ``forward_unfused``: rs_gru_fwd, the attention
+    layer's composed scores, rs_augru_fwd.  ``forward_ids`` takes the behaviour
+    features' ids and tables instead of gathered rows (rs_dien_evolution_ids_fwd:
+    the keys are never written to HBM).  ``out`` (a [B, >= D] view with unit
+    column stride) receives hist in place; ``want_h1`` / ``want_scores`` also
+    return H1 [B, T, D] / the scores [B, T]."""
+
+    def __init__(self, embedding_size, att_hidden_units=(64, 16), att_activation="sigmoid",
+                 att_weight_normalization=False, gru_type="AUGRU", augru_update="reference", device=None, seed=None):
+        super().__init__(device, seed)
+        D = int(embedding_size)
+        if augru_update not in _DIEN_UPDATES:
+            raise ValueError(f"augru_update must be 'reference' or 'paper', got {augru_update!r}")
+        self.embedding_size, self.augru_update = D, augru_update
+        self.gru1 = GRU(D, return_sequences=True, device=device, seed=_subseed(self._gen), input_dim=D)
+        self.attention = AttentionSequencePoolingLayer(att_hidden_units, att_activation, att_weight_normalization,
+                                                       return_score=True, device=device, seed=_subseed(self._gen),
+                                                       input_dim=D)
+        self.gru2 = AUGRU(D, gru_type=gru_type, augru_update=augru_update, device=device, seed=_subseed(self._gen),
+                          input_dim=D)
+
+    def keras_weights(self):
+        out = {f"gru1/{k}": v for k, v in self.gru1.keras_weights().items()}
+        out.update({f"attention_sequence_pooling_layer/{k}": v for k, v in self.attention.keras_weights().items()})
+        out.update({f"gru2/{k}": v for k, v in self.gru2.keras_weights().items()})
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        own = self.keras_weights()
+        if strict and set(own) != set(weights):
+            raise KeyError(f"InterestEvolution: expected weights {sorted(own)}, got {sorted(weights)}")
+        with torch.no_grad():
+            for name, p in own.items():
+                if name in weights:
+                    p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
+        self._weights_changed()
+
+    def _invalidate(self):
+        self.__dict__.pop("_dien_prep", None)
+
+    def _hidden(self):
+        h = self.attention.att_hidden_units
+        return (C.c_int * max(len(h), 1))(*h)
+
+    def fused_ok(self, T):
+        a = self.attention
+        act = _DIEN_ACTS.get(a.att_activation)
+        return bool(act is not None and not a.local_att.dnn.use_bn and _lib.lib().rs_dien_evolution_ok(
+            int(T), self.embedding_size, len(a.att_hidden_units), self._hidden(), act))
+
+    def prepared(self):
+        """The weights packed for the one-launch form (rs_dien_prepare), cached until one changes."""
+        key = tuple((p._version, p.data_ptr()) for p in self.keras_weights().values())
+        ent = self.__dict__.get("_dien_prep")
+        if ent is None or ent[0] != key:
+            a, la = self.attention, self.attention.local_att
+            n, D = len(a.att_hidden_units), self.embedding_size
+            size = _lib.lib().rs_dien_prepared_size(D, n, self._hidden())
+            if size < 0:
+                _lib.check(-1, "rs_dien_prepared_size")
+            pa = lambda ts: (C.c_void_p * n)(*[ptr(t) for t in ts])
+            ls = list(la.dnn.layers)
+            dice = a.att_activation == "dice"
+            prep = torch.empty(size, dtype=torch.float32, device=self._dev)
+            call("rs_dien_prepare", D, ptr(self.gru1.kernel), ptr(self.gru1.recurrent_kernel), ptr(self.gru1.bias),
+                 ptr(self.gru2.cell.kernel), ptr(self.gru2.cell.recurrent_kernel), n, self._hidden(),
+                 _DIEN_ACTS[a.att_activation], pa([l.kernel for l in ls]), pa([l.bias for l in ls]),
+                 pa([l.dice.moving_mean for l in ls]) if dice else None,
+                 pa([l.dice.moving_variance for l in ls]) if dice else None,
+                 pa([l.dice.alphas for l in ls]) if dice else None, ptr(la.kernel), ptr(la.bias), ptr(prep), _stream())
+            ent = self.__dict__["_dien_prep"] = (key, prep)
+        return ent[1]
+
+    def _outputs(self, B, T, out, want_h1, want_scores):
+        D = self.embedding_size
+        if out is None:
+            out = torch.empty(B, D, dtype=torch.float32, device=self._dev)
+        if out.dim() != 2 or out.shape[0] != B or out.shape[1] < D or (B and out.stride(1) != 1):
+            raise ValueError("InterestEvolution: out must be a [batch, >= D] view with unit column stride")
+        h1 = torch.empty(B, T, D, dtype=torch.float32, device=self._dev) if want_h1 else None
+        sc = torch.empty(B, T, dtype=torch.float32, device=self._dev) if want_scores else None
+        return out, h1, sc
+
+    def _tail_args(self, T):
+        a = self.attention
+        return (T, self.embedding_size, len(a.att_hidden_units), self._hidden(), _DIEN_ACTS[a.att_activation],
+                1 if a.weight_normalization else 0, _DIEN_UPDATES[self.augru_update], ptr(self.prepared()))
+
+    @staticmethod
+    def _ret(out, h1, sc, want_h1, want_scores):
+        if not (want_h1 or want_scores):
+            return out
+        return (out,) + ((h1,) if want_h1 else ()) + ((sc,) if want_scores else ())
+
+    def forward_fused(self, keys, query, seq_length, out=None, want_h1=False, want_scores=False):
+        keys = _seq_input(keys, self._dev, "InterestEvolution")
+        B, T, D = keys.shape
+        if D != self.embedding_size:
+            raise ValueError(f"InterestEvolution built for width {self.embedding_size}, got {D}")
+        q = query if (torch.is_tensor(query) and query.is_cuda and query.dtype == torch.float32) \
+            else _to_device_f32(query, self._dev)
+        q = q.reshape(B, D)
+        q = q if (not B or q.stride(1) == 1) else q.contiguous()
+        L = _lengths(seq_length, self._dev, B)
+        out, h1, sc = self._outputs(B, T, out, want_h1, want_scores)
+        call("rs_dien_evolution_fwd", ptr(keys), keys.stride(0), keys.stride(1), ptr(q), q.stride(0), ptr(L),
+             _lib.id_kind(L), *self._tail_args(T), ptr(h1), ptr(sc), ptr(out), out.stride(0), B, _stream())
+        return self._ret(out[:, :D], h1, sc, want_h1, want_scores)
+
+    def forward_ids(self, hist_ids, cand_ids, tables, seq_length, out=None, want_h1=False, want_scores=False,
+                    check_ids=True, err=None):
+        """hist_ids[f] [B, T], cand_ids[f] [B] and tables[f] [vocab_f, width_f]
+        per behaviour feature (1..4, widths adding up to D).  err: the caller's
+        device error flag (its own check follows), else one is made here."""
+        n = len(tables)
+        hs = [_ids_tensor(h, self._dev) for h in hist_ids]
+        cs = [_ids_tensor(c, self._dev).reshape(-1).to(h.dtype).contiguous() for c, h in zip(cand_ids, hs)]
+        hs = [h if h.stride(1) == 1 else h.contiguous() for h in hs]
+        B, T = hs[0].shape
+        L = _lengths(seq_length, self._dev, B)
+        out, h1, sc = self._outputs(B, T, out, want_h1, want_scores)
+        err = err if err is not None else _ErrFlag(self._dev)
+        ia = lambda v: (C.c_int * n)(*v)
+        la = lambda v: (C.c_int64 * n)(*v)
+        pa = lambda ts: (C.c_void_p * n)(*[ptr(t) for t in ts])
+        call("rs_dien_evolution_ids_fwd", n, ia([t.shape[1] for t in tables]), ia([_lib.id_kind(h) for h in hs]),
+             pa(hs), la([h.stride(0) for h in hs]), pa(cs), la([1] * n), pa(tables), la([t.shape[0] for t in tables]),
+             ptr(L), _lib.id_kind(L), *self._tail_args(T), ptr(h1), ptr(sc), ptr(out), out.stride(0), B, ptr(err.t),
+             _stream())
+        if check_ids:
+            err.check("InterestEvolution")
+        return self._ret(out[:, :self.embedding_size], h1, sc, want_h1, want_scores)
+
+    def forward_unfused(self, keys, query, seq_length, out=None, want_h1=False, want_scores=False):
+        keys = _seq_input(keys, self._dev, "InterestEvolution")
+        B, T, D = keys.shape
+        h1 = self.gru1(keys)
+        sc = self.attention([query, h1, seq_length]).reshape(B, T)
+        hist = self.gru2(h1, sc)
+        if out is not None:
+            out[:, :D] = hist
+            hist = out[:, :D]
+        return self._ret(hist, h1, sc, want_h1, want_scores)
+
+    def forward(self, keys, query, seq_length, **kw):
+        T = torch.as_tensor(keys).shape[1] if not torch.is_tensor(keys) else keys.shape[1]
+        return (self.forward_fused if self.fused_ok(T) else self.forward_unfused)(keys, query, seq_length, **kw)
+
+
+class PredictionLayer(KerasModule):
+    """PredictionLayer(task='binary', use_bias=True) — layer/core.py:223-256:
+    sigmoid(x + global_bias) for 'binary', x + global_bias for 'regression';
+    ``global_bias`` [1] zeros.  Output [B, 1]."""
+
+    def __init__(self, task="binary", use_bias=True, device=None):
+        super().__init__(device)
+        if task not in ("binary", "multiclass", "regression"):
+            raise ValueError("task must be binary,multiclass or regression")
+        self.task, self.use_bias = task, bool(use_bias)
+        self.global_bias = nn.Parameter(torch.zeros(1, device=self._dev), requires_grad=False) if use_bias else None
+        self._one = None
+
+    def forward(self, inputs):
+        x = inputs if (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32) \
+            else _to_device_f32(inputs, self._dev)
+        x = x.reshape(-1, 1).contiguous()
+        if self._one is None:
+            self._one = torch.ones(1, device=self._dev)
+            self._zero = torch.zeros(1, device=self._dev)
+        out = torch.empty_like(x)
+        if x.shape[0]:
+            call("rs_affine_act", ptr(x), 1, ptr(self._one), ptr(self.global_bias if self.use_bias else self._zero),
+                 None, _lib.ACT["sigmoid"] if self.task == "binary" else 0, ptr(out), 1, x.shape[0], 1, _stream())
         return out

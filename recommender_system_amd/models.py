@@ -21,6 +21,8 @@ models (Hcyand/recommender_system, algorithm/deep_learning/model/):
   WideDeep(feature_columns, hidden_units, output_dim, activation) model/wideDeep.py:14-34
   MMOE(mmoe_hidden_units, num_experts, num_tasks, tower_hidden_units, output_dim,
        activation='relu', use_expert_bias=True, use_gate_bias=True) model/mmoe.py:10-32
+  DIEN(dnn_feature_columns, history_feature_list, gru_type='GRU', ...)
+                                                                  model/dien.py:83-169
 
 Criteo-style models take the reference's packed input X[B, 13+F] (dense
 features followed by label-encoded sparse ids, as floats — Keras casts them to
@@ -51,7 +53,9 @@ from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense,
                      FGCNNLayer, FMLayer, InnerProductLayer, OuterProductLayer,
                      KerasModule, ResLayer, TowerMixin, WideLayer, sigmoid_combine, _ids_tensor, _to_device_f32,
                      _AFM_MODES, _ErrFlag, _RES_MAXH, _RES_MAXU, _res_key, _res_ok, _res_prepare, mmoe_layer, tower_layer,
-                     _MMOE_MAXL, _mmoe_dims, _mmoe_input, _mmoe_ok, _mmoe_params, _mmoe_prepare)
+                     _MMOE_MAXL, _mmoe_dims, _mmoe_input, _mmoe_ok, _mmoe_params, _mmoe_prepare,
+                     DNN, InterestEvolution, PredictionLayer, _glorot_normal)
+from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, build_input_features
 
 
 from ._train_ops import (_Dropout, _check_train_tower, _dnn_apply, _dnn_backward, _dnn_train_forward,  # noqa: F401
@@ -1766,3 +1770,250 @@ class MMOE(KerasModule):
         if self.fused_ok():
             return self.forward_fused(x)
         return self.forward_unfused(x)
+
+
+class DIEN(TowerMixin, KerasModule):
+    """DIEN(dnn_feature_columns, history_feature_list, gru_type='GRU',
+    use_negsampling=False, alpha=1.0, use_bn=False, dnn_hidden_units=(256, 128,
+    64), dnn_activation='relu', att_hidden_units=(64, 16), att_activation='dice',
+    att_weight_normalization=True, l2_reg_dnn=0, l2_reg_embedding=1e-6,
+    dnn_dropout=0., seed=1024, task='binary') — model/dien.py:83-169, forward
+    only.  ``forward(inputs)`` takes the reference's feature dict (name ->
+    array; ``seq_length`` holds the behaviour lengths, dien.py:197-203) and
+    returns [B, 1].
+
+    The behaviour features (``history_feature_list``, their ``hist_`` var-len
+    columns) go through InterestEvolution — ONE launch from the ids when the
+    shape fits (``forward``), rs_gru_fwd / composed scores / rs_augru_fwd
+    otherwise and in ``forward_unfused`` — whose hist [B, D] lands in the tower
+    input [every SparseFeat's row, in column order | pooled other var-len
+    features | hist | dense values].  The tower DNN(dnn_hidden_units,
+    dnn_activation, use_bn) + Dense(1, use_bias=False) + PredictionLayer is one
+    rs_mlp_fwd launch for a BN-free 'relu' / 'sigmoid' tower (global_bias is the
+    head unit's bias), composed layer by layer otherwise.  One table per
+    ``embedding_name``, shared by candidate, history and negative-history
+    columns.  Other var-len columns need a ``length_name`` and are pooled
+    ('mean' / 'sum' / 'max') with torch ops.
+
+    As in the reference: ``gru_type`` has no effect (AUGRU never passes it to
+    its cell) and ``use_negsampling`` only adds a training loss, which is not
+    built — the ``neg_`` columns are accepted and unused; l2 / dropout / alpha
+    are training-only.  ``augru_update='paper'`` (an extension) uses the DIEN
+    paper's blend h <- (1 - z) h + z hh instead of the reference's.
+
+    Keras weight names (``keras_weights`` / ``set_keras_weights`` round-trip;
+    not verified against a live Keras graph — TensorFlow is not available to
+    the tests): ``sparse_emb_{embedding_name}/embeddings`` or, when a var-len
+    column shares the name, ``sparse_seq_emb_{last such column}/embeddings``;
+    ``gru1/{kernel, recurrent_kernel, bias}``;
+    ``attention_sequence_pooling_layer/local_att/{kernel, bias,
+    dnn/kernel{i}, dnn/bias{i}, dnn/dice{i}/{dice_alpha, bn/moving_mean,
+    bn/moving_variance}}``; ``gru2/{kernel, recurrent_kernel}``;
+    ``dnn/{kernel{i}, bias{i}, bn{i}/{gamma, beta, moving_mean,
+    moving_variance}, dice{i}/…, alpha{i}}``; ``dense/kernel``;
+    ``prediction_layer/global_bias``."""
+
+    def __init__(self, dnn_feature_columns, history_feature_list, gru_type="GRU", use_negsampling=False, alpha=1.0,
+                 use_bn=False, dnn_hidden_units=(256, 128, 64), dnn_activation="relu", att_hidden_units=(64, 16),
+                 att_activation="dice", att_weight_normalization=True, l2_reg_dnn=0, l2_reg_embedding=1e-6,
+                 dnn_dropout=0., seed=1024, task="binary", augru_update="reference", device=None):
+        super().__init__(device, seed)
+        cols = list(dnn_feature_columns)
+        build_input_features(cols)  # (raises the reference's TypeError on a foreign column)
+        self.feature_columns, self.history_feature_list = cols, list(history_feature_list)
+        self.gru_type, self.use_negsampling, self.alpha, self.task = gru_type, bool(use_negsampling), alpha, task
+        self.sparse_cols = [c for c in cols if isinstance(c, SparseFeat)]
+        self.dense_cols = [c for c in cols if isinstance(c, DenseFeat)]
+        varlen = [c for c in cols if isinstance(c, VarLenSparseFeat)]
+        hist_names = ["hist_" + n for n in self.history_feature_list]
+        neg_names = ["neg_" + n for n in hist_names]
+        self.history_cols = [c for c in varlen if c.name in hist_names]
+        self.neg_history_cols = [c for c in varlen if c.name in neg_names]
+        self.pooled_cols = [c for c in varlen if c.name not in hist_names and c.name not in neg_names]
+        self.query_cols = [c for c in self.sparse_cols if c.name in self.history_feature_list]
+        n_hist = len(self.history_feature_list)
+        if not n_hist or len(self.history_cols) != n_hist or len(self.query_cols) != n_hist:
+            raise ValueError("DIEN: every feature of history_feature_list needs a SparseFeat and a 'hist_' "
+                             "VarLenSparseFeat")
+        for qc, hc in zip(self.query_cols, self.history_cols):
+            if hc.name != "hist_" + qc.name or hc.embedding_dim != qc.embedding_dim:
+                raise ValueError(f"DIEN: behaviour columns {qc.name!r} / {hc.name!r} do not pair (order or width)")
+        lens = {c.length_name for c in self.history_cols}
+        if len(lens) != 1 or None in lens:
+            raise ValueError("DIEN: the history columns need one common length_name")
+        self.length_name = lens.pop()
+        for c in self.pooled_cols:
+            if c.length_name is None:
+                raise ValueError(f"DIEN: var-len column {c.name!r} needs a length_name (no Keras mask reaches its "
+                                 "pooling: the embeddings are built with seq_mask_zero=False)")
+            if c.combiner not in ("sum", "mean", "max"):
+                raise ValueError("mode must be sum or mean")
+        self.maxlen = self.history_cols[0].maxlen
+        # one table per embedding_name; a later var-len column replaces the entry (utils/inputs.py:33-43)
+        spec = {}
+        for c in self.sparse_cols:
+            spec[c.embedding_name] = (f"sparse_emb_{c.embedding_name}", c)
+        for c in varlen:
+            spec[c.embedding_name] = (f"sparse_seq_emb_{c.name}", c)
+        self._table_names = {en: kn for en, (kn, _) in spec.items()}
+        self.tables = torch.nn.ParameterDict()
+        for en, (kn, c) in spec.items():
+            shape = (int(c.vocabulary_size), int(c.embedding_dim))
+            init = c.embeddings_initializer
+            w = torch.randn(*shape, generator=self._gen).mul_(1e-4) if init is None else \
+                torch.as_tensor(init(shape, self._gen), dtype=torch.float32).reshape(shape)
+            self.tables[en] = torch.nn.Parameter(w.to(self._dev), requires_grad=False)
+        for c in cols:
+            if not isinstance(c, DenseFeat) and tuple(self.tables[c.embedding_name].shape) != \
+                    (int(c.vocabulary_size), int(c.embedding_dim)):
+                raise ValueError(f"DIEN: column {c.name!r} does not match the table of {c.embedding_name!r}")
+        D = sum(c.embedding_dim for c in self.history_cols)
+        self.evolution = InterestEvolution(D, att_hidden_units, att_activation, att_weight_normalization,
+                                           gru_type=gru_type, augru_update=augru_update, device=device,
+                                           seed=_subseed(self._gen))
+        # tower input columns
+        col = 0
+        self._sparse_at, self._pooled_at, self._dense_at = [], [], []
+        for c in self.sparse_cols:
+            self._sparse_at.append(col)
+            col += c.embedding_dim
+        for c in self.pooled_cols:
+            self._pooled_at.append(col)
+            col += c.embedding_dim
+        self._hist_at = col
+        col += D
+        for c in self.dense_cols:
+            self._dense_at.append(col)
+            col += c.dimension
+        self.input_width = col
+        self.dnn = DNN(dnn_hidden_units, dnn_activation, l2_reg_dnn, dnn_dropout, use_bn, device=device,
+                       seed=_subseed(self._gen), input_dim=col)
+        self.prediction_layer = PredictionLayer(task, device=device)
+        last = self.dnn.hidden_units[-1] if self.dnn.hidden_units else col
+        self.dense = Dense(1, None, device=device, seed=_subseed(self._gen), input_dim=last)
+        with torch.no_grad():
+            self.dense.kernel.copy_(_glorot_normal(last, 1, self._gen, self._dev))
+        self.dense.bias = self.prediction_layer.global_bias  # Dense(1, use_bias=False) + the head's bias: one unit
+
+    # ---- weights
+    def keras_weights(self):
+        out = {f"{self._table_names[en]}/embeddings": t for en, t in self.tables.items()}
+        out.update(self.evolution.keras_weights())
+        out.update(_prefixed("dnn", self.dnn.keras_weights()))
+        out["dense/kernel"] = self.dense.kernel
+        out["prediction_layer/global_bias"] = self.prediction_layer.global_bias
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        own = self.keras_weights()
+        if strict and set(own) != set(weights):
+            raise KeyError(f"DIEN: missing {sorted(set(own) - set(weights))}, unknown {sorted(set(weights) - set(own))}")
+        with torch.no_grad():
+            for name, p in own.items():
+                if name in weights:
+                    p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
+        self._weights_changed()
+
+    def _layers(self):
+        return list(self.dnn.layers) + [self.dense]
+
+    def tower_fused_ok(self):
+        return (not self.dnn.use_bn and self.task in ("binary", "regression")
+                and all(l.activation in ("relu", "sigmoid") for l in self.dnn.layers) and self.tower_ok())
+
+    # ---- inputs
+    def _ids(self, inputs, col, seq):
+        t = _ids_tensor(inputs[col.name], self._dev)
+        if seq and (t.dim() != 2 or t.shape[1] != col.maxlen):
+            raise ValueError(f"DIEN: {col.name!r} has shape {tuple(t.shape)}, expected [batch, {col.maxlen}]")
+        return (t if seq else t.reshape(-1)).contiguous()
+
+    def _rows(self, ids, table, bad):
+        """table[ids] with an out-of-range id as a zero row (torch ops; bad collects the flag)."""
+        ok = (ids >= 0) & (ids < table.shape[0])
+        bad.append(~ok.all())
+        return table[torch.where(ok, ids, torch.zeros_like(ids)).long()] * ok.unsqueeze(-1)
+
+    def _tower_input(self, inputs, err, bad):
+        """[B, input_width] with every column but hist filled; the batch size."""
+        first = self.sparse_cols[0] if self.sparse_cols else self.history_cols[0]
+        B = int(torch.as_tensor(inputs[first.name]).shape[0])
+        x = torch.empty(B, self.input_width, dtype=torch.float32, device=self._dev)
+        pieces = [(c.embedding_dim, at, self._ids(inputs, c, False), self.tables[c.embedding_name])
+                  for c, at in zip(self.sparse_cols, self._sparse_at)]
+        for c, at in zip(self.dense_cols, self._dense_at):
+            v = _to_device_f32(inputs[c.name], self._dev).reshape(B, c.dimension)
+            pieces.append((c.dimension, at, v, None))
+        for i in range(0, len(pieces) if B else 0, 16):
+            ch = pieces[i:i + 16]
+            n = len(ch)
+            call("rs_concat_pieces", n, (C.c_int * n)(*[p[0] for p in ch]), (C.c_int * n)(*[p[1] for p in ch]),
+                 (C.c_int * n)(*[-1 if p[3] is None else _lib.id_kind(p[2]) for p in ch]),
+                 (C.c_void_p * n)(*[ptr(p[2]) for p in ch]),
+                 (C.c_int64 * n)(*[p[2].stride(0) if p[3] is None else 1 for p in ch]),
+                 (C.c_void_p * n)(*[ptr(p[3]) for p in ch]),
+                 (C.c_int64 * n)(*[0 if p[3] is None else p[3].shape[0] for p in ch]), ptr(x), x.stride(0), B,
+                 ptr(err.t), _lib.stream())
+        for c, at in zip(self.pooled_cols, self._pooled_at):
+            ids = self._ids(inputs, c, True)
+            e = self._rows(ids, self.tables[c.embedding_name], bad)
+            L = torch.as_tensor(inputs[c.length_name]).reshape(-1).to(self._dev)
+            m = (torch.arange(c.maxlen, device=self._dev).unsqueeze(0) < L.unsqueeze(1)).to(torch.float32).unsqueeze(-1)
+            if c.combiner == "max":  # layer/sequence.py:76-78
+                v = (e - (1 - m) * 1e9).max(dim=1).values
+            else:
+                v = (e * m).sum(1)
+                if c.combiner == "mean":
+                    v = v / (L.to(torch.float32).unsqueeze(1) + 1e-8)
+            x[:, at:at + c.embedding_dim] = v
+        return x, B
+
+    def _tower(self, x, fused):
+        if fused:
+            return self.tower(x, head=self.task == "binary")
+        y = self.dnn(x)
+        logit = torch.empty(y.shape[0], 1, dtype=torch.float32, device=self._dev)
+        if y.shape[0]:
+            call("rs_dense_fwd", ptr(y), y.stride(0), ptr(self.dense.kernel), None, None, 0, ptr(logit), 1, y.shape[0],
+                 y.shape[1], 1, _lib.stream())
+        return self.prediction_layer(logit)
+
+    def _check(self, err, bad, check_ids):
+        if check_ids:
+            err.check("DIEN")
+            if bad and bool(torch.stack(bad).any()):
+                raise _lib.BadIdError("DIEN: embedding id out of range (indices must be in [0, vocab))")
+
+    def forward(self, inputs, check_ids=True):
+        err, bad = _ErrFlag(self._dev), []
+        x, B = self._tower_input(inputs, err, bad)
+        ev, D = self.evolution, self.evolution.embedding_size
+        hist_out = x[:, self._hist_at:self._hist_at + D]
+        hs = [self._ids(inputs, c, True) for c in self.history_cols]
+        cs = [self._ids(inputs, c, False) for c in self.query_cols]
+        tabs = [self.tables[c.embedding_name] for c in self.history_cols]
+        if B and ev.fused_ok(self.maxlen) and len(tabs) <= 4:
+            ev.forward_ids(hs, cs, tabs, inputs[self.length_name], out=hist_out, check_ids=False, err=err)
+        elif B:
+            keys = torch.cat([self._rows(h, t, bad) for h, t in zip(hs, tabs)], dim=-1)
+            q = torch.cat([self._rows(c, t, bad) for c, t in zip(cs, tabs)], dim=-1)
+            ev(keys, q, inputs[self.length_name], out=hist_out)
+        self._check(err, bad, check_ids)
+        return self._tower(x, self.tower_fused_ok())
+
+    def forward_unfused(self, inputs, check_ids=True):
+        """The same forward from the stand-alone entries: torch gathers,
+        rs_gru_fwd, the composed attention scores, rs_augru_fwd, then the tower
+        layer by layer."""
+        err, bad = _ErrFlag(self._dev), []
+        x, B = self._tower_input(inputs, err, bad)
+        ev, D = self.evolution, self.evolution.embedding_size
+        hs = [self._ids(inputs, c, True) for c in self.history_cols]
+        cs = [self._ids(inputs, c, False) for c in self.query_cols]
+        tabs = [self.tables[c.embedding_name] for c in self.history_cols]
+        if B:
+            keys = torch.cat([self._rows(h, t, bad) for h, t in zip(hs, tabs)], dim=-1)
+            q = torch.cat([self._rows(c, t, bad) for c, t in zip(cs, tabs)], dim=-1)
+            ev.forward_unfused(keys, q, inputs[self.length_name], out=x[:, self._hist_at:self._hist_at + D])
+        self._check(err, bad, check_ids)
+        return self._tower(x, False)
