@@ -913,6 +913,84 @@ int rs_augru_fwd(const float* x, int64_t x_bstride, int64_t x_tstride,
                  float* last, int64_t last_stride, int64_t batch,
                  rs_stream_t stream);
 
+/* ------------------------- training of DIEN's recurrences (dien_train.hip)
+ * Backpropagation through time of the GRU and the AUGRU above, gate order
+ * z r h.  Steps run t = T-1 .. 0, padded positions included; dh is the
+ * upstream gradient of h_t: dseq[b, t] where given, plus dlast at t = T-1,
+ * plus the carry from step t + 1.
+ * GRU, a_z = xi_z + hr_z, a_r = xi_r + hr_r, c = xi_h + r hr_h:
+ *   dz = dh (h_prev - hh)   dhh = dh (1 - z)   dc = dhh (1 - hh^2)
+ *   da_z = dz z (1 - z)     dr = dc hr_h       da_r = dr r (1 - r)
+ *   gx = [da_z, da_r, dc]   gh = [da_z, da_r, dc r]   carry = dh z + gh U^T
+ * AUGRU, u = hsig(a_z), z = a u, r = hsig(a_r), a = scores[b, t]:
+ *   reference blend: dz = dh (h_prev - hh), keep = dh z,       dhh = dh (1 - z)
+ *   paper blend:     dz = dh (hh - h_prev), keep = dh (1 - z), dhh = dh z
+ *   dc = dhh (1 - hh^2)   d(rh) = dc U_h^T   dr = d(rh) h_prev
+ *   da[b, t] = sum_units dz u   da_z = dz a hsig'(a_z)   da_r = dr hsig'(a_r)
+ *   (hsig' = 0.2 where 0 < hsig < 1, else 0)   gx = [da_z, da_r, dc]
+ *   carry = keep + d(rh) r + [da_z, da_r] U_zr^T
+ * rs_gru_train_fwd / rs_augru_train_fwd: rs_gru_fwd / rs_augru_fwd (the same
+ * device functions: seq / last are bit-identical to theirs) that also write
+ * `saved`, rs_gru_saved_size / rs_augru_saved_size(T, din, units, batch) =
+ * batch * T * 5 * Up / batch * T * 4 * Up floats (Up = roundup(units, 16);
+ * -1 on a bad shape): per (b, t) the planes z | r | hh | hr_h | h_prev (GRU)
+ * or u | r | hh | h_prev (AUGRU), Up floats each.  saved is 16-byte aligned.
+ * As in rs_gru_fwd, at least one of seq / last is required.
+ * rs_gru_prepare_bwd: the transposed recurrent kernel [units, 3 units] as MFMA
+ * fragments (rs_gru_bwd_prepared_size(units) = 3 * Up * Up floats: gate, unit
+ * tile c, k-group g, lane l, element j = U[16 c + (l & 15)][gate * units + 16 g
+ * + 4 (l >> 4) + j], zero padded); one image serves both recurrences.
+ * rs_gru_bwd (dseq [B, T, units] contiguous and / or dlast [B, units], rows
+ * dlast_stride apart; one of them may be NULL) and rs_augru_bwd (dlast
+ * required) are one launch over 16-sample tiles with only the h -> h chain in
+ * the time loop.  They write the operands of everything off the chain as
+ * contiguous matrices of B * T rows (row b * T + t):
+ *   gx [B T, 3 units]; GRU: gh [B T, 3 units] and hprev [B T, units] (row t =
+ *   0 is zeros); AUGRU: hrh [B T, 2 units] = [h_prev | r h_prev]
+ * so that with x as [B T, din]
+ *   dx = gx W^T, dW = x^T gx, GRU: dU = hprev^T gh, dbias = [colsum gx; colsum
+ *   gh]; AUGRU: dU[:, :2 units] = h_prev^T gx[:, :2 units], dU[:, 2 units:] =
+ *   (r h_prev)^T gx[:, 2 units:]
+ * are rs_gemm / rs_col_sum_split calls.  rs_augru_bwd also returns the
+ * gradient of the scores through the forward's mask (scores: the forward's
+ * output, rows scores_stride apart; len, weight_norm as in the forward):
+ *   weight_norm: ds_t = p_t (da_t - sum_{tau < len} p_tau da_tau) for t < len
+ *   else:        ds_t = da_t for t < len;   exactly 0 for t >= len
+ * (a row with len <= 0 is all zeros), and the raw da [B, T] where da is not
+ * NULL.  Caps: units <= 64 (din <= 64 in the forwards); no cap on T: saved
+ * state and upstream gradients are read step by step from global memory.
+ * Deterministic; the per-sample results (gx, gh, hprev, hrh, ds, da) do not
+ * depend on the batch or its tile mates, and neither does dx = gx W^T when
+ * its rs_gemm is called without a workspace (one pass over K = 3 units; with
+ * one, the number of K slices follows the batch).  Stream-ordered,
+ * graph-capturable; arguments are validated before any device work; nothing
+ * is launched for batch 0; every element of every output is written.       */
+int64_t rs_gru_saved_size(int T, int din, int units, int64_t batch);
+int64_t rs_augru_saved_size(int T, int din, int units, int64_t batch);
+int64_t rs_gru_bwd_prepared_size(int units);
+int rs_gru_prepare_bwd(int units, const float* recurrent, float* prepared_bwd,
+                       rs_stream_t stream);
+int rs_gru_train_fwd(const float* x, int64_t x_bstride, int64_t x_tstride,
+                     int T, int din, int units, const float* prepared,
+                     float* seq, float* last, int64_t last_stride,
+                     float* saved, int64_t batch, rs_stream_t stream);
+int rs_augru_train_fwd(const float* x, int64_t x_bstride, int64_t x_tstride,
+                       const float* scores, int64_t scores_stride, int T,
+                       int din, int units, int augru_update,
+                       const float* prepared, float* last,
+                       int64_t last_stride, float* saved, int64_t batch,
+                       rs_stream_t stream);
+int rs_gru_bwd(const float* saved, const float* dseq, const float* dlast,
+               int64_t dlast_stride, int T, int units,
+               const float* prepared_bwd, float* gx, float* gh, float* hprev,
+               int64_t batch, rs_stream_t stream);
+int rs_augru_bwd(const float* saved, const float* scores,
+                 int64_t scores_stride, const void* len, int len_kind,
+                 int weight_norm, const float* dlast, int64_t dlast_stride,
+                 int T, int units, int augru_update,
+                 const float* prepared_bwd, float* gx, float* hrh, float* ds,
+                 float* da, int64_t batch, rs_stream_t stream);
+
 /* ------------------------------------------ wide part of Wide&Deep (a17)
  * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
  * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense

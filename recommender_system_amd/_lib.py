@@ -112,6 +112,14 @@ SIGNATURES = {
     "rs_gru_prepare": (I, [I, I, P, P, P, P, P]),
     "rs_gru_fwd": (I, [P, L, L, I, I, I, P, P, P, L, L, P]),
     "rs_augru_fwd": (I, [P, L, L, P, L, I, I, I, I, P, P, L, L, P]),
+    "rs_gru_saved_size": (L, [I, I, I, L]),
+    "rs_augru_saved_size": (L, [I, I, I, L]),
+    "rs_gru_bwd_prepared_size": (L, [I]),
+    "rs_gru_prepare_bwd": (I, [I, P, P, P]),
+    "rs_gru_train_fwd": (I, [P, L, L, I, I, I, P, P, P, L, P, L, P]),
+    "rs_augru_train_fwd": (I, [P, L, L, P, L, I, I, I, I, P, P, L, P, L, P]),
+    "rs_gru_bwd": (I, [P, P, P, L, I, I, P, P, P, P, L, P]),
+    "rs_augru_bwd": (I, [P, P, L, P, I, I, P, L, I, I, I, P, P, P, P, P, L, P]),
     "rs_wide_onehot_fwd":(I, [P, I, L, P, L, I, P, P, I, P, P, P, L, P, P]),
     "rs_concat_pieces": (I, [I, P, P, P, P, P, P, P, P, L, L, P, P]),
     "rs_deepfm_fused_ok": (I, [I, I, I, I, I, P]),

@@ -4,7 +4,8 @@ Plain functions over the librs_hip entry points, one per piece of plumbing
 that every ``train_step`` needs: grow-only scratch buffers, the row-sparse
 embedding update, the BCE head, one Dense layer's backward, the DNNLayer
 forward with saved activations and its backward, DNNLayer's Dropout, training
-BatchNormalization, and the FM part of a DeepFM step.  A step keeps its own
+BatchNormalization, the forward and backward of DIEN's two recurrences, and
+the FM part of a DeepFM step.  A step keeps its own
 launches in its own body, in order; only what repeated from step to step lives
 here.  Nothing here chooses a kernel or changes what a step requests: each
 caller passes the sizes and workspace it passed when the lines were its own
@@ -275,6 +276,168 @@ def bn_train_bwd(bn, x, saved, dy, st):
     call("rs_bn_train_bwd", ptr(x), x.stride(0), B, D, ptr(saved[0]), ptr(saved[1]), ptr(bn.gamma), bn.epsilon,
          ptr(dy), dy.stride(0), ptr(dx), D, ptr(dgamma), ptr(dbeta), st)
     return dx, dgamma, dbeta
+
+
+# ------------------------------------- Dense + activation blocks of DIEN's step
+def dense_train_need(shapes):
+    """Workspace bytes for DenseTrain over (K_in, N_out, rows) layer shapes:
+    the split-K gemms in both orientations, the column sums, Dice."""
+    lb = _lib.lib()
+    need = [gemm_need(list(shapes) + [(m, kin, n) for kin, n, m in shapes])]
+    need += [lb.rs_col_sum_workspace_size(m, n) for _, n, m in shapes]
+    need += [lb.rs_dice_train_workspace_size(m, n) for _, n, m in shapes]
+    return max(need)
+
+
+class DenseTrain:
+    """Dense layers with 'relu' / 'sigmoid' / 'dice' activations inside a
+    training step (DNN's layers, LocalActivationUnit's, the auxiliary net's):
+    rs_dense_fwd without activation, rs_dice_train_fwd/_bwd in training mode
+    (the batch's statistics, moving averages moved with momentum 0.99),
+    dense_backward.  relu, sigmoid and their backward (dy [y > 0], dy y (1 -
+    y)) are torch elementwise ops.  ``updates`` collects (weight, gradient, l2)."""
+
+    def __init__(self, gw, st, device):
+        self.gw, self.st, self.updates = gw, st, []
+        self.emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device)
+
+    def dense(self, xin, layer, m):
+        n = layer.kernel.shape[1]
+        z = self.emp(m, n)
+        call("rs_dense_fwd", ptr(xin), xin.stride(0), ptr(layer.kernel), ptr(layer.bias), None, _lib.ACT[None], ptr(z),
+             n, m, layer.kernel.shape[0], n, self.st)
+        return z
+
+    def act_fwd(self, layer, z, m):
+        """(what the backward needs, the activation's output)."""
+        if layer.activation == "dice":
+            d, n = layer.dice, z.shape[1]
+            mu, vr, y = self.emp(n), self.emp(n), self.emp(m, n)
+            call("rs_dice_train_fwd", ptr(z), m, n, ptr(d.alphas), d.epsilon, 0.99, ptr(d.moving_mean),
+                 ptr(d.moving_variance), ptr(mu), ptr(vr), ptr(y), *self.gw, self.st)
+            return (mu, vr), y
+        return None, (torch.relu(z) if layer.activation == "relu" else torch.sigmoid(z))
+
+    def act_bwd(self, layer, z, y, saved, dy, m):
+        if layer.activation == "dice":
+            d, n = layer.dice, z.shape[1]
+            dz, dal = self.emp(m, n), self.emp(n)
+            call("rs_dice_train_bwd", ptr(z), m, n, ptr(d.alphas), ptr(saved[0]), ptr(saved[1]), d.epsilon, ptr(dy),
+                 ptr(dz), ptr(dal), *self.gw, self.st)
+            self.updates.append((d.alphas, dal, 0.0))
+            return dz
+        return dy * (y > 0) if layer.activation == "relu" else dy * y * (1 - y)
+
+    def dense_bwd(self, layer, a_in, dz, l2=0.0):
+        """dL/d(a_in); the kernel's and bias's gradients go to ``updates``."""
+        dW, db, below = dense_backward(layer.kernel, a_in, dz.contiguous(), self.gw, self.emp, self.st, split_sum=True)
+        self.updates.extend([(layer.kernel, dW, l2), (layer.bias, db, 0.0)])
+        return below
+
+
+# ------------------------------------------- DIEN's recurrences (dien_train.hip)
+def _rnn_saved(size_fn, what, T, din, units, B, device):
+    n = getattr(_lib.lib(), size_fn)(T, din, units, B)
+    if n < 0:
+        _lib.check(-1, what)
+    return torch.empty(max(n, 1), dtype=torch.float32, device=device)
+
+
+def _rnn_ws(owner, M, din, U):
+    """(workspace, bytes) for the weight-gradient gemms and column sums of a
+    recurrence's backward at M = B T rows (the dx gemm takes none)."""
+    need = gemm_need([(din, 3 * U, M), (U, 3 * U, M)])
+    return gemm_ws(owner, max(need, _lib.lib().rs_col_sum_workspace_size(M, 3 * U)))
+
+
+def gru_train_forward(gru, x, st):
+    """GRU forward of a training step (rs_gru_train_fwd): (seq [B, T, units],
+    saved) — seq is bit-identical to ``gru(x)``'s, saved is what gru_backward
+    reads."""
+    x = gru._input(x)
+    B, T, din = x.shape
+    if T < 1:
+        raise ValueError("GRU: an empty sequence")
+    saved = _rnn_saved("rs_gru_saved_size", "rs_gru_saved_size", T, din, gru.units, B, x.device)
+    seq = torch.empty(B, T, gru.units, dtype=torch.float32, device=x.device)
+    call("rs_gru_train_fwd", ptr(x), x.stride(0), x.stride(1), T, din, gru.units, ptr(gru.prepared()), ptr(seq), None,
+         0, ptr(saved), B, st)
+    return seq, saved
+
+
+def gru_backward(gru, x, saved, dseq, dlast, st, d_in=True):
+    """Backward of gru_train_forward from dseq = dL/dseq [B, T, units] and / or
+    dlast = dL/d(last state) [B, units]: one rs_gru_bwd launch for the chain,
+    then rs_gemm / rs_col_sum_split at M = B T.  Returns (dx [B, T, din] or
+    None, dkernel, drecurrent_kernel, dbias [2, 3 units])."""
+    B, T, din = x.shape
+    U, M = gru.units, B * T
+    emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
+    x = x.contiguous()
+    dseq = None if dseq is None else dseq.reshape(B, T, U).contiguous()
+    dlast = None if dlast is None else dlast.reshape(B, U).contiguous()
+    gx, gh, hp = emp(M, 3 * U), emp(M, 3 * U), emp(M, U)
+    call("rs_gru_bwd", ptr(saved), ptr(dseq), ptr(dlast), U, T, U, ptr(gru.prepared_bwd()), ptr(gx), ptr(gh), ptr(hp),
+         B, st)
+    gw = _rnn_ws(gru, M, din, U)
+    dW, dU, db = emp(din, 3 * U), emp(U, 3 * U), emp(2, 3 * U)
+    call("rs_gemm", 1, 0, din, 3 * U, M, 1.0, ptr(x), din, ptr(gx), 3 * U, 0.0, ptr(dW), 3 * U, None, 0, *gw, st)
+    call("rs_gemm", 1, 0, U, 3 * U, M, 1.0, ptr(hp), U, ptr(gh), 3 * U, 0.0, ptr(dU), 3 * U, None, 0, *gw, st)
+    call("rs_col_sum_split", ptr(gx), 3 * U, M, 3 * U, ptr(db[0]), *gw, st)
+    call("rs_col_sum_split", ptr(gh), 3 * U, M, 3 * U, ptr(db[1]), *gw, st)
+    dx = None
+    if d_in:
+        dx = emp(B, T, din)
+        # no workspace: always one pass over K = 3 U, so a sample's dx never depends on the batch
+        call("rs_gemm", 0, 1, M, din, 3 * U, 1.0, ptr(gx), 3 * U, ptr(gru.kernel), 3 * U, 0.0, ptr(dx), din, None, 0,
+             None, 0, st)
+    return dx, dW, dU, db
+
+
+def augru_train_forward(augru, x, scores, st):
+    """AUGRU forward of a training step (rs_augru_train_fwd): (last [B, units],
+    saved), last bit-identical to ``augru(x, scores)``'s."""
+    c = augru.cell
+    x = c._input(x)
+    B, T, din = x.shape
+    a = scores.reshape(B, T).to(torch.float32).contiguous()
+    saved = _rnn_saved("rs_augru_saved_size", "rs_augru_saved_size", T, din, c.units, B, x.device)
+    last = torch.empty(B, c.units, dtype=torch.float32, device=x.device)
+    call("rs_augru_train_fwd", ptr(x), x.stride(0), x.stride(1), ptr(a), a.stride(0), T, din, c.units,
+         _layers._DIEN_UPDATES[augru.augru_update], ptr(c.prepared()), ptr(last), last.stride(0), ptr(saved), B, st)
+    return last, saved
+
+
+def augru_backward(augru, x, scores, lengths, weight_norm, saved, dlast, st, want_da=False):
+    """Backward of augru_train_forward from dlast = dL/d(last state): one
+    rs_augru_bwd launch (the chain, da and the masked softmax's backward),
+    then rs_gemm at M = B T.  ``scores`` are the forward's (masked, normalised
+    when weight_norm), ``lengths`` [B] their mask.  Returns (dx [B, T, din],
+    ds [B, T] = dL/d(unmasked scores), da or None, dkernel,
+    drecurrent_kernel)."""
+    c = augru.cell
+    B, T, din = x.shape
+    U, M = c.units, B * T
+    emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
+    x = x.contiguous()
+    a = scores.reshape(B, T).to(torch.float32).contiguous()
+    dlast = dlast.reshape(B, U).contiguous()
+    gx, hrh, ds = emp(M, 3 * U), emp(M, 2 * U), emp(B, T)
+    da = emp(B, T) if want_da else None
+    call("rs_augru_bwd", ptr(saved), ptr(a), T, ptr(lengths), _lib.id_kind(lengths), 1 if weight_norm else 0,
+         ptr(dlast), U, T, U, _layers._DIEN_UPDATES[augru.augru_update], ptr(c.prepared_bwd()), ptr(gx), ptr(hrh),
+         ptr(ds), ptr(da), B, st)
+    gw = _rnn_ws(c, M, din, U)
+    dW, dU, dx = emp(din, 3 * U), emp(U, 3 * U), emp(B, T, din)
+    call("rs_gemm", 1, 0, din, 3 * U, M, 1.0, ptr(x), din, ptr(gx), 3 * U, 0.0, ptr(dW), 3 * U, None, 0, *gw, st)
+    # dU_zr = h_prev^T [da_z, da_r], dU_h = (r h_prev)^T dc: column blocks of hrh, gx and dU
+    call("rs_gemm", 1, 0, U, 2 * U, M, 1.0, ptr(hrh), 2 * U, ptr(gx), 3 * U, 0.0, ptr(dU), 3 * U, None, 0, *gw, st)
+    call("rs_gemm", 1, 0, U, U, M, 1.0, hrh.data_ptr() + 4 * U, 2 * U, gx.data_ptr() + 8 * U, 3 * U, 0.0,
+         dU.data_ptr() + 8 * U, 3 * U, None, 0, *gw, st)
+    # no workspace: always one pass over K = 3 U, so a sample's dx never depends on the batch
+    call("rs_gemm", 0, 1, M, din, 3 * U, 1.0, ptr(gx), 3 * U, ptr(c.kernel), 3 * U, 0.0, ptr(dx), din, None, 0, None,
+         0, st)
+    return dx, ds, da, dW, dU
 
 
 # ------------------------------------------------ FM part of a DeepFM step

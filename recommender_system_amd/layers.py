@@ -54,6 +54,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import call, ptr
+from . import _train_ops
 from ._train_ops import _subseed, scratch
 
 _DEFAULT_DEVICE = "cuda"
@@ -1646,6 +1647,7 @@ class _Recurrent(KerasModule):
 
     def _invalidate(self):
         self.__dict__.pop("_rnn_prep", None)
+        self.__dict__.pop("_rnn_prep_bwd", None)
 
     def prepared(self):
         ps = [p for p in (self.kernel, self.recurrent_kernel, self.bias) if p is not None]
@@ -1659,6 +1661,21 @@ class _Recurrent(KerasModule):
             call("rs_gru_prepare", self.input_dim, self.units, ptr(self.kernel), ptr(self.recurrent_kernel),
                  ptr(self.bias), ptr(prep), _stream())
             ent = self.__dict__["_rnn_prep"] = (key, prep)
+        return ent[1]
+
+    def prepared_bwd(self):
+        """The transposed recurrent kernel packed for rs_gru_bwd / rs_augru_bwd
+        (rs_gru_prepare_bwd), cached per weight version."""
+        p = self.recurrent_kernel
+        key = (p._version, p.data_ptr())
+        ent = self.__dict__.get("_rnn_prep_bwd")
+        if ent is None or ent[0] != key:
+            size = _lib.lib().rs_gru_bwd_prepared_size(self.units)
+            if size < 0:
+                _lib.check(-1, "rs_gru_bwd_prepared_size")
+            prep = torch.empty(size, dtype=torch.float32, device=self._dev)
+            call("rs_gru_prepare_bwd", self.units, ptr(p), ptr(prep), _stream())
+            ent = self.__dict__["_rnn_prep_bwd"] = (key, prep)
         return ent[1]
 
     def _input(self, inputs):
@@ -1703,6 +1720,17 @@ class GRU(_Recurrent):
         call("rs_gru_fwd", ptr(x), x.stride(0), x.stride(1), T, self.input_dim, u, ptr(self.prepared()), None,
              ptr(last), last.stride(0), B, _stream())
         return last
+
+    def train_forward(self, inputs):
+        """(seq [B, T, units], saved): the forward of a training step
+        (rs_gru_train_fwd; seq bit-identical to forward's)."""
+        return _train_ops.gru_train_forward(self, inputs, _stream())
+
+    def backward(self, x, saved, dseq=None, dlast=None, d_in=True):
+        """(dx, dkernel, drecurrent_kernel, dbias) from the gradient of the
+        sequence [B, T, units] and / or of the last state [B, units]
+        (rs_gru_bwd, then rs_gemm / rs_col_sum_split)."""
+        return _train_ops.gru_backward(self, self._input(x), saved, dseq, dlast, _stream(), d_in)
 
 
 class AUGRUCell(_Recurrent):
@@ -1751,6 +1779,21 @@ class AUGRU(KerasModule):
         call("rs_augru_fwd", ptr(x), x.stride(0), x.stride(1), ptr(a), a.stride(0), T, c.input_dim, c.units,
              _DIEN_UPDATES[self.augru_update], ptr(c.prepared()), ptr(last), last.stride(0), B, _stream())
         return last
+
+    def train_forward(self, inputs, att_score):
+        """(last [B, units], saved) (rs_augru_train_fwd; last bit-identical to forward's)."""
+        a = att_score if (torch.is_tensor(att_score) and att_score.is_cuda) else _to_device_f32(att_score, self._dev)
+        return _train_ops.augru_train_forward(self, inputs, a, _stream())
+
+    def backward(self, x, att_score, seq_length, saved, dlast, weight_normalization=False, want_da=False):
+        """(dx, ds, da, dkernel, drecurrent_kernel) from the gradient of the
+        last state.  ``att_score`` [B, T] are the masked (and, with
+        weight_normalization, softmax-normalised) scores the forward took and
+        ``seq_length`` [B] their mask: ds is the gradient of the scores before
+        the mask, da (want_da) that of att_score itself."""
+        x = self.cell._input(x)
+        L = _lengths(seq_length, self._dev, x.shape[0])
+        return _train_ops.augru_backward(self, x, att_score, L, weight_normalization, saved, dlast, _stream(), want_da)
 
 
 class DNN(KerasModule):
@@ -2103,6 +2146,83 @@ class InterestEvolution(KerasModule):
             out[:, :D] = hist
             hist = out[:, :D]
         return self._ret(hist, h1, sc, want_h1, want_scores)
+
+    def train_forward(self, keys, query, seq_length):
+        """The forward of a training step: (hist [B, D], H1 [B, T, D], ctx).
+        Always the composed form — rs_gru_train_fwd; the attention unit at M =
+        B T rows (rs_din_att_concat for [q, k, q - k, q k], rs_dense_fwd per
+        layer, then rs_dice_train_fwd or relu / sigmoid, the score Dense, mask
+        and softmax); rs_augru_train_fwd.  'dice' runs in training mode, as
+        Dice.call(training=True) does: the batch's statistics over all B T
+        rows, padded positions included, moving averages moved with momentum
+        0.99 — which the one-launch kernel cannot provide.  relu / sigmoid, the
+        mask and the softmax are torch elementwise ops.  ctx is what
+        ``train_backward`` reads."""
+        a, la = self.attention, self.attention.local_att
+        if la.dnn.use_bn or any(l.activation not in ("relu", "sigmoid", "dice") for l in la.dnn.layers):
+            raise NotImplementedError("InterestEvolution.train_forward: att_activation 'relu', 'sigmoid' or 'dice' only")
+        st = _stream()
+        keys = _seq_input(keys, self._dev, "InterestEvolution").contiguous()
+        B, T, D = keys.shape
+        if D != self.embedding_size:
+            raise ValueError(f"InterestEvolution built for width {self.embedding_size}, got {D}")
+        q = query if (torch.is_tensor(query) and query.is_cuda and query.dtype == torch.float32) \
+            else _to_device_f32(query, self._dev)
+        q = q.reshape(B, D).contiguous()
+        L = _lengths(seq_length, self._dev, B)
+        M, layers = B * T, list(la.dnn.layers)
+        shapes = [(l.kernel.shape[0], l.kernel.shape[1], M) for l in layers] + [(la.kernel.shape[0], 1, M)]
+        dt = _train_ops.DenseTrain(_train_ops.gemm_ws(self, _train_ops.dense_train_need(shapes)), st, self._dev)
+        H1, sv1 = _train_ops.gru_train_forward(self.gru1, keys, st)
+        e0 = dt.emp(M, 4 * D)
+        call("rs_din_att_concat", ptr(q), ptr(H1), B, T, D, ptr(e0), st)
+        a_in, a_pre, a_saved = [e0], [], []
+        for l in layers:
+            z = dt.dense(a_in[-1], l, M)
+            saved, y = dt.act_fwd(l, z, M)
+            a_pre.append(z), a_saved.append(saved), a_in.append(y)
+        raw = dt.dense(a_in[-1], la, M).reshape(B, T)
+        valid = torch.arange(T, device=self._dev).unsqueeze(0) < L.unsqueeze(1)
+        if a.weight_normalization:
+            scores = torch.softmax(torch.where(valid, raw, torch.full_like(raw, float(-2 ** 32 + 1))), dim=-1)
+        else:
+            scores = torch.where(valid, raw, torch.zeros_like(raw))
+        hist, sv2 = _train_ops.augru_train_forward(self.gru2, H1, scores, st)
+        ctx = dict(keys=keys, q=q, L=L, H1=H1, sv1=sv1, sv2=sv2, scores=scores, a_in=a_in, a_pre=a_pre,
+                   a_saved=a_saved, dt=dt)
+        return hist, H1, ctx
+
+    def train_backward(self, ctx, dhist, dh1=None):
+        """The backward of ``train_forward`` from dhist = dL/d(hist) [B, D] and,
+        optionally, dh1 = a gradient that reaches H1 from elsewhere (DIEN's
+        auxiliary loss) [B, T, D]: rs_augru_bwd (the chain and the scores'
+        gradient through the mask), the attention unit reversed (split-K
+        rs_gemm / rs_col_sum_split, rs_dice_train_bwd) into
+        rs_din_att_concat_bwd, which adds into dH1 and dq, then rs_gru_bwd.
+        Returns (dkeys [B, T, D], dq [B, D], [(weight, gradient, l2)]) for every
+        weight of ``keras_weights()`` that trains; nothing is updated here."""
+        a, la = self.attention, self.attention.local_att
+        dt, st, H1, q = ctx["dt"], ctx["dt"].st, ctx["H1"], ctx["q"]
+        B, T, D = H1.shape
+        M, layers = B * T, list(la.dnn.layers)
+        first = len(dt.updates)
+        dH1, ds, _, dW2, dU2 = _train_ops.augru_backward(self.gru2, H1, ctx["scores"], ctx["L"], a.weight_normalization,
+                                                         ctx["sv2"], dhist, st)
+        c2 = self.gru2.cell
+        dt.updates.extend([(c2.kernel, dW2, 0.0), (c2.recurrent_kernel, dU2, 0.0)])
+        a_in, a_pre, a_saved = ctx["a_in"], ctx["a_pre"], ctx["a_saved"]
+        d_in = dt.dense_bwd(la, a_in[-1], ds.reshape(M, 1))
+        for i in reversed(range(len(layers))):
+            dz = dt.act_bwd(layers[i], a_pre[i], a_in[i + 1], a_saved[i], d_in, M)
+            d_in = dt.dense_bwd(layers[i], a_in[i], dz)
+        dq = torch.zeros(B, D, dtype=torch.float32, device=self._dev)
+        call("rs_din_att_concat_bwd", ptr(d_in), ptr(q), ptr(H1), B, T, D, ptr(dq), D, ptr(dH1), st)
+        if dh1 is not None:
+            dH1 += dh1
+        g1 = self.gru1
+        dkeys, dW1, dU1, db1 = _train_ops.gru_backward(g1, ctx["keys"], ctx["sv1"], dH1, None, st)
+        dt.updates.extend([(g1.kernel, dW1, 0.0), (g1.recurrent_kernel, dU1, 0.0), (g1.bias, db1, 0.0)])
+        return dkeys, dq, dt.updates[first:]
 
     def forward(self, keys, query, seq_length, **kw):
         T = torch.as_tensor(keys).shape[1] if not torch.is_tensor(keys) else keys.shape[1]

@@ -47,7 +47,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, _train_ops
 from ._lib import call, ptr
 from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense, DNNLayer, EmbedLayer, FFMLayer,
                      FGCNNLayer, FMLayer, InnerProductLayer, OuterProductLayer,
@@ -1777,8 +1777,8 @@ class DIEN(TowerMixin, KerasModule):
     use_negsampling=False, alpha=1.0, use_bn=False, dnn_hidden_units=(256, 128,
     64), dnn_activation='relu', att_hidden_units=(64, 16), att_activation='dice',
     att_weight_normalization=True, l2_reg_dnn=0, l2_reg_embedding=1e-6,
-    dnn_dropout=0., seed=1024, task='binary') — model/dien.py:83-169, forward
-    only.  ``forward(inputs)`` takes the reference's feature dict (name ->
+    dnn_dropout=0., seed=1024, task='binary') — model/dien.py:83-169.
+    ``forward(inputs)`` takes the reference's feature dict (name ->
     array; ``seq_length`` holds the behaviour lengths, dien.py:197-203) and
     returns [B, 1].
 
@@ -1796,9 +1796,10 @@ class DIEN(TowerMixin, KerasModule):
     ('mean' / 'sum' / 'max') with torch ops.
 
     As in the reference: ``gru_type`` has no effect (AUGRU never passes it to
-    its cell) and ``use_negsampling`` only adds a training loss, which is not
-    built — the ``neg_`` columns are accepted and unused; l2 / dropout / alpha
-    are training-only.  ``augru_update='paper'`` (an extension) uses the DIEN
+    its cell) and ``use_negsampling`` only adds a training loss — the ``neg_``
+    columns are unused in the forward; l2 / dropout / alpha are training-only
+    (``train_step``; the auxiliary loss's net is ``auxiliary_nn``, present only
+    with ``use_negsampling``, with its own ``keras_weights()``).  ``augru_update='paper'`` (an extension) uses the DIEN
     paper's blend h <- (1 - z) h + z hh instead of the reference's.
 
     Keras weight names (``keras_weights`` / ``set_keras_weights`` round-trip;
@@ -1894,6 +1895,12 @@ class DIEN(TowerMixin, KerasModule):
         with torch.no_grad():
             self.dense.kernel.copy_(_glorot_normal(last, 1, self._gen, self._dev))
         self.dense.bias = self.prediction_layer.global_bias  # Dense(1, use_bias=False) + the head's bias: one unit
+        self._l2_reg_embedding = l2_reg_embedding
+        self.last_aux_loss = None
+        # the auxiliary loss's net (dien.py:40), seeded after every other weight: a given seed gives the
+        # same model with and without it.  Its weights are its own keras_weights(), not the model's.
+        self.auxiliary_nn = DNN([100, 50, 1], "sigmoid", device=device, seed=_subseed(self._gen), input_dim=2 * D) \
+            if self.use_negsampling else None
 
     # ---- weights
     def keras_weights(self):
@@ -2017,3 +2024,198 @@ class DIEN(TowerMixin, KerasModule):
             ev.forward_unfused(keys, q, inputs[self.length_name], out=x[:, self._hist_at:self._hist_at + D])
         self._check(err, bad, check_ids)
         return self._tower(x, False)
+
+    # ---- training
+    def _check_train(self):
+        if self._dev.type != "cuda":
+            raise NotImplementedError("DIEN.train_step: training runs only on a HIP device")
+        if self.task != "binary":
+            raise NotImplementedError("DIEN.train_step: task 'binary' only (binary cross-entropy on the sigmoid output)")
+        if any(l.activation not in ("relu", "dice") for l in self.dnn.layers):
+            raise NotImplementedError("DIEN.train_step: dnn_activation 'relu' or 'dice' only")
+        la = self.evolution.attention.local_att
+        if la.dnn.use_bn or any(l.activation not in ("relu", "sigmoid", "dice") for l in la.dnn.layers):
+            raise NotImplementedError("DIEN.train_step: att_activation 'relu', 'sigmoid' or 'dice' only")
+        if any(c.combiner == "max" for c in self.pooled_cols):
+            raise NotImplementedError("DIEN.train_step: pooled var-len columns train with 'sum' or 'mean' only "
+                                      "('max' has no training step)")
+        if self.use_negsampling:
+            if len(self.neg_history_cols) != len(self.history_cols):
+                raise ValueError("DIEN.train_step: use_negsampling needs a 'neg_hist_' column per behaviour feature")
+            if self.maxlen < 2:
+                raise ValueError("DIEN.train_step: use_negsampling needs T >= 2 (the auxiliary loss is a mean over "
+                                 "B (T - 1) positions)")
+
+    def _table_sgd(self, table, ids, grad, lr, st):
+        """Row-sparse SGD of one id source of a table: ids (any shape, n
+        lookups) with dL/d(row) = grad [n, k] (unit column stride);
+        rs_embedding_sgd with one field at offset 0, duplicates summed in lookup
+        order."""
+        ids = ids.reshape(-1, 1)
+        n, (V, k) = ids.shape[0], table.shape
+        meta = self.__dict__.setdefault("_sgd_meta", {})
+        if V not in meta:
+            meta[V] = (torch.zeros(1, dtype=torch.int64, device=self._dev),
+                       torch.full((1,), V, dtype=torch.int64, device=self._dev))
+        ws = scratch(self, "_emb_ws", _lib.lib().rs_embedding_sgd_workspace_size(n))
+        call("rs_embedding_sgd", ptr(table), V, k, ptr(ids), _lib.id_kind(ids), 1, ptr(meta[V][0]), ptr(meta[V][1]), 1,
+             n, ptr(grad), grad.stride(-2), float(lr), ptr(ws), None, st)
+
+    def train_step(self, inputs, labels, lr=0.01, return_loss=False, check_ids=True, dropout=None):
+        """One step of Keras ``fit`` with SGD(lr) and binary cross-entropy on
+        the sigmoid output (model/dien.py:226-231), every gradient computed
+        before any update.  Returns the per-sample BCE losses [B] (before the
+        step) with ``return_loss``; the scalar auxiliary loss of the step is
+        left in ``last_aux_loss``.
+          forward: the rows of every id source (torch gathers), then
+          InterestEvolution.train_forward — rs_gru_train_fwd,
+          the attention unit composed at M = B T rows (rs_din_att_concat,
+          rs_dense_fwd per layer, rs_dice_train_fwd in training mode — the
+          batch's statistics over all B T rows, moving averages moved with
+          momentum 0.99 — or relu / sigmoid, the score Dense, mask and softmax),
+          rs_augru_train_fwd, then the tower layer by layer (rs_dense_fwd,
+          rs_bn_train_fwd with use_bn, relu or rs_dice_train_fwd, the dropout
+          draw) and the logit;
+          backward: rs_head_grad, split-K rs_gemm / rs_col_sum_split per Dense,
+          rs_dice_train_bwd / rs_bn_train_bwd, then
+          InterestEvolution.train_backward — rs_augru_bwd (the chain, the
+          scores' gradient through the mask), the attention unit reversed into
+          rs_din_att_concat_bwd, rs_gru_bwd;
+          update: one rs_sgd_update_multi over the dense parameters (l2_reg_dnn
+          on the tower kernels), rs_l2_decay (l2_reg_embedding) on every table
+          and rs_embedding_sgd per id source (candidate, history, negative
+          history, pooled 'sum' / 'mean' columns; candidates receive the
+          tower-input gradient plus the attention query's).
+        With ``use_negsampling`` the auxiliary loss (dien.py:20-51) is added:
+        ``auxiliary_nn`` on [H1[:, :-1], keys[:, 1:]] and [H1[:, :-1],
+        neg_keys[:, 1:]], mask t < len - 1, -log sigmoid as softplus, total =
+        BCE + alpha aux; its weights are trained.
+        relu, sigmoid and their backward (dy [y > 0], dy y (1 - y)), the masks
+        and the auxiliary loss's softplus are torch elementwise ops on device
+        tensors.  ``dropout``: None applies dnn_dropout, False turns it off, a
+        float overrides the rate."""
+        self._check_train()
+        dev, st = self._dev, _lib.stream()
+        ev, dnn = self.evolution, self.dnn
+        D, T = ev.embedding_size, self.maxlen
+        rate = 0.0 if dropout is False else float(dnn.dropout_rate or 0) if dropout in (None, True) else float(dropout)
+
+        # ---- inputs: every id is checked before any weight changes
+        err, bad = _ErrFlag(dev), []
+        x, B = self._tower_input(inputs, err, bad)
+        hs = [self._ids(inputs, c, True) for c in self.history_cols]
+        cs = [self._ids(inputs, c, False) for c in self.query_cols]
+        tabs = [self.tables[c.embedding_name] for c in self.history_cols]
+        keys = torch.cat([self._rows(h, t, bad) for h, t in zip(hs, tabs)], dim=-1).contiguous()
+        q = torch.cat([self._rows(c, t, bad) for c, t in zip(cs, tabs)], dim=-1).contiguous()
+        ns, neg = [], None
+        if self.use_negsampling:
+            ns = [self._ids(inputs, c, True) for c in self.neg_history_cols]
+            neg = torch.cat([self._rows(h, t, bad) for h, t in zip(ns, tabs)], dim=-1)
+        self._check(err, bad, check_ids)
+        labels = _to_device_f32(labels, dev).reshape(-1)
+        M, M2 = B * T, B * (T - 1)
+        tower = list(dnn.layers)
+        aux_layers = list(self.auxiliary_nn.layers) if self.use_negsampling else []
+        shapes = [(l.kernel.shape[0], l.kernel.shape[1], B) for l in tower] + [(self.dense.kernel.shape[0], 1, B)]
+        shapes += [(l.kernel.shape[0], l.kernel.shape[1], 2 * M2) for l in aux_layers]
+        dt = _train_ops.DenseTrain(gemm_ws(self, _train_ops.dense_train_need(shapes)), st, dev)
+        updates = dt.updates  # (weight, gradient, l2)
+
+        # ---- forward
+        hist, H1, ctx = ev.train_forward(keys, q, inputs[self.length_name])
+        L = ctx["L"]
+        x[:, self._hist_at:self._hist_at + D] = hist
+        t_in, t_pre, t_bn, t_saved = [x], [], [], []
+        drop = (_dropout_rng(self), rate, []) if rate > 0 else None
+        for i, l in enumerate(tower):
+            z = dt.dense(t_in[-1], l, B)
+            bn_saved = None
+            if dnn.use_bn:
+                t_bn.append(z)
+                bn_saved, z = bn_train_fwd(dnn.bn_layers[i], z, st)
+            saved, y = dt.act_fwd(l, z, B)
+            if drop is not None:
+                drop[2].append(drop[0].draw(y, rate, st))
+            t_pre.append(z), t_saved.append((bn_saved, saved)), t_in.append(y)
+        logit = dt.dense(t_in[-1], self.dense, B).reshape(B)
+        g, loss = bce_head_logit(logit, labels, return_loss, st)
+
+        # ---- backward: the tower
+        dh = dt.dense_bwd(self.dense, t_in[-1], g.view(B, 1))
+        for i in reversed(range(len(tower))):
+            l = tower[i]
+            if drop is not None:
+                drop[0].redraw(dh, rate, drop[2][i], st)
+            dz = dt.act_bwd(l, t_pre[i], t_in[i + 1], t_saved[i][1], dh, B)
+            if dnn.use_bn:
+                bn = dnn.bn_layers[i]
+                dz, dgam, dbet = bn_train_bwd(bn, t_bn[i], t_saved[i][0], dz.contiguous(), st)
+                updates.extend([(bn.gamma, dgam, 0.0), (bn.beta, dbet, 0.0)])
+            dh = dt.dense_bwd(l, t_in[i], dz, l2=float(dnn.l2_reg or 0))
+        if drop is not None:
+            drop[0].end_step(st)
+        dx = dh  # [B, input_width]
+
+        # ---- the auxiliary loss: its gradient reaches H1[:, :-1], the history rows 1.. and the negative rows
+        dh1_aux = dkeys_aux = dneg = None
+        self.last_aux_loss = None
+        if self.use_negsampling:
+            # auxiliary_nn on the click rows then the no-click rows: one pass over 2 B (T - 1) rows
+            h = H1[:, :-1].reshape(M2, D)
+            u_in = [torch.cat([torch.cat([h, keys[:, 1:].reshape(M2, D)], 1),
+                               torch.cat([h, neg[:, 1:].reshape(M2, D)], 1)], 0)]
+            for l in aux_layers[:-1]:
+                u_in.append(torch.sigmoid(dt.dense(u_in[-1], l, 2 * M2)))
+            z3 = dt.dense(u_in[-1], aux_layers[-1], 2 * M2).reshape(2, B, T - 1)
+            amask = (torch.arange(T - 1, device=dev).unsqueeze(0) < (L - 1).unsqueeze(1)).to(torch.float32)
+            sp = torch.nn.functional.softplus
+            self.last_aux_loss = ((sp(-z3[0]) + sp(z3[1])) * amask).sum() / M2
+            sg = torch.sigmoid(z3)
+            dz = torch.stack([(sg[0] - 1) * amask, sg[1] * amask]).mul_(float(self.alpha) / M2).reshape(2 * M2, 1)
+            for i in reversed(range(len(aux_layers))):
+                if i < len(aux_layers) - 1:
+                    dz = dz * u_in[i + 1] * (1 - u_in[i + 1])
+                dz = dt.dense_bwd(aux_layers[i], u_in[i], dz)
+            zeros = lambda: torch.zeros(B, T, D, dtype=torch.float32, device=dev)
+            dh1_aux, dneg = zeros(), zeros()
+            dh1_aux[:, :-1] = (dz[:M2, :D] + dz[M2:, :D]).reshape(B, T - 1, D)
+            dkeys_aux = dz[:M2, D:].reshape(B, T - 1, D)
+            dneg[:, 1:] = dz[M2:, D:].reshape(B, T - 1, D)
+
+        # ---- backward: the interest evolution
+        dkeys, dq, ev_updates = ev.train_backward(ctx, dx[:, self._hist_at:self._hist_at + D], dh1=dh1_aux)
+        updates = updates + ev_updates
+        if dkeys_aux is not None:
+            dkeys[:, 1:] += dkeys_aux
+
+        # ---- update
+        _lib.sgd_update_multi([(w, gr, gr.numel(), l2) for w, gr, l2 in updates], lr, st)
+        l2e = float(self._l2_reg_embedding or 0)
+        if l2e:
+            for t in self.tables.values():
+                call("rs_l2_decay", ptr(t), t.numel(), float(lr), l2e, st)
+        qcol = {c.name: i for i, c in enumerate(self.query_cols)}
+        offs = [0]
+        for c in self.history_cols:
+            offs.append(offs[-1] + c.embedding_dim)
+        for c, at in zip(self.sparse_cols, self._sparse_at):
+            gr = dx[:, at:at + c.embedding_dim]
+            if c.name in qcol:  # a candidate: the tower-input gradient plus the attention query's
+                o = offs[qcol[c.name]]
+                gr = gr + dq[:, o:o + c.embedding_dim]
+            self._table_sgd(self.tables[c.embedding_name], self._ids(inputs, c, False), gr.contiguous(), lr, st)
+        for i, c in enumerate(self.history_cols):
+            w = c.embedding_dim
+            self._table_sgd(tabs[i], hs[i], dkeys[:, :, offs[i]:offs[i] + w].reshape(M, w).contiguous(), lr, st)
+            if dneg is not None:
+                self._table_sgd(tabs[i], ns[i], dneg[:, :, offs[i]:offs[i] + w].reshape(M, w).contiguous(), lr, st)
+        for c, at in zip(self.pooled_cols, self._pooled_at):
+            Lc = torch.as_tensor(inputs[c.length_name]).reshape(-1).to(dev)
+            m = (torch.arange(c.maxlen, device=dev).unsqueeze(0) < Lc.unsqueeze(1)).to(torch.float32)
+            if c.combiner == "mean":
+                m = m / (Lc.to(torch.float32).unsqueeze(1) + 1e-8)
+            gr = (m.unsqueeze(-1) * dx[:, at:at + c.embedding_dim].unsqueeze(1)).reshape(-1, c.embedding_dim)
+            self._table_sgd(self.tables[c.embedding_name], self._ids(inputs, c, True), gr.contiguous(), lr, st)
+        self._weights_changed()
+        return loss

@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .models import AFM, DCN, DIN, FFM, FM, NFM, DeepCrossing, DeepFM, WideDeep
+from .models import AFM, DCN, DIEN, DIN, FFM, FM, NFM, DeepCrossing, DeepFM, WideDeep
 
 
 def compile_fit(model, dense, ids, labels, field_vocab=None, batch_size=32, epochs=10, sgd=0.01, device=None):
@@ -30,16 +30,16 @@ def compile_fit(model, dense, ids, labels, field_vocab=None, batch_size=32, epoc
     widths are ``field_vocab``, or its embedding layer's vocab when that is
     not given; the offsets are their cumulative sum).  PNN trains with its
     own loop in the reference (model/pnn.py:74-81): PNN.train_step."""
-    if not isinstance(model, (FM, DeepFM, DCN, NFM, FFM, AFM, DeepCrossing, WideDeep, DIN)):
-        raise NotImplementedError("compile_fit: FM, DeepFM, DCN, NFM, FFM, AFM, DeepCrossing, WideDeep and DIN "
+    if not isinstance(model, (FM, DeepFM, DCN, NFM, FFM, AFM, DeepCrossing, WideDeep, DIN, DIEN)):
+        raise NotImplementedError("compile_fit: FM, DeepFM, DCN, NFM, FFM, AFM, DeepCrossing, WideDeep, DIN and DIEN "
                                   "(PNN: PNN.train_step)")
     dev = torch.device(device) if device is not None else model._dev
     labels = torch.as_tensor(np.asarray(labels, np.float32), device=dev)
     N = labels.shape[0]
     history = []
-    if isinstance(model, DIN):
+    if isinstance(model, (DIN, DIEN)):
         if ids is not None:
-            raise ValueError("compile_fit(DIN): pass the input dict as `dense` and ids=None")
+            raise ValueError(f"compile_fit({type(model).__name__}): pass the input dict as `dense` and ids=None")
         data = {key: torch.as_tensor(np.asarray(val), device=dev) for key, val in dense.items()}
         for _ in range(epochs):
             losses = [model.train_step({key: val[r0:r0 + batch_size] for key, val in data.items()},
