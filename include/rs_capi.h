@@ -991,6 +991,119 @@ int rs_augru_bwd(const float* saved, const float* scores,
                  const float* prepared_bwd, float* gx, float* hrh, float* ds,
                  float* da, int64_t batch, rs_stream_t stream);
 
+/* ------------------------------------- DSSM two-tower retrieval (a20), forward
+ * model/dssm.py:17-90: a user tower and an item tower, each
+ *   [SparseFeat rows | pooled var-len features | dense values]  ->  DNN  ->
+ *   tf.math.l2_normalize(axis=-1)
+ * (layer/utils.py:140-150, utils/inputs.py:142-153), then the in-batch
+ * sampled-softmax loss (layer/activation.py:267-285, layer/utils.py:206-215)
+ * or the 'logistic' score.
+ *
+ * rs_seq_pool_fwd: SequencePoolingLayer (layer/sequence.py:20-95), 1..8
+ * features per launch.  Feature f pools T = Ts[f] positions of widths[f] = E
+ * columns into out[b * out_stride + out_cols[f] ..]; combiners[f] = 0 sum,
+ * 1 mean, 2 max.  Source: kinds[f] = RS_ID_*: ids srcs[f] [B, T] (rows
+ * src_strides[f] elements apart) looked up in tables[f] [vocabs[f], E] (an id
+ * outside [0, vocab) at a valid position reads a zero row and sets
+ * *err_flag); kinds[f] = -1: embedded values srcs[f] [B, T, E] fp32 (samples
+ * src_strides[f] floats apart), the layer's own call.  Mask: lengths[f] [B]
+ * (len_kinds[f] = RS_ID_I32 / RS_ID_I64; position t valid iff t < len, the
+ * supports_masking=False form) or, with lengths[f] NULL (lengths itself may be
+ * NULL), the supports_masking=True form: an id source's mask is id != 0 (Keras
+ * mask_zero), a dense source's is masks[f] (uint8 [B, T], non-zero = valid),
+ * and the length is the number of valid positions.
+ *   sum  = the valid rows added;  mean = sum / (float(len) + 1e-8) — a length
+ *   above T keeps all T positions and divides by the length given, a length
+ *   <= 0 gives 0;  max = max of x - (1 - mask) * 1e9: masked rows are skipped
+ *   and stand as -1e9, exact while |x| < 32 (beyond that the reference's
+ *   x - 1e9 keeps some of x's bits; a documented deviation).
+ * One wave per (sample, feature).  A row is read by E / 4 lanes (float4; E
+ * lanes when 4 does not divide E or the rows are not 16-byte aligned), so the
+ * wave holds G = min(64 / lanes-per-row, 16) rows at once.  Sum order, fixed
+ * per sample and independent of the batch: lane group g adds positions t = g,
+ * g + G, g + 2 G, ... ascending, starting from 0; the G partial rows are then
+ * added in group order, ((p_0 + p_1) + p_2) + ...  The rows of masked
+ * positions are not loaded (the ids of all T positions are).  Caps: E <= 64,
+ * or a multiple of 4 up to 256.
+ *
+ * rs_dssm_tower_fwd: one tower in one launch over 16-sample tiles.  The
+ * single-id and dense pieces are rs_concat_pieces' (n_pieces, widths, in_cols
+ * = first input column, kinds, srcs, src_strides, tables, vocabs), the
+ * sequence pieces rs_seq_pool_fwd's (n_seq, seq_*, combiners, lengths,
+ * len_kinds, masks); together 1..16 pieces that tile the dims[0] input columns
+ * exactly.  The row is staged in LDS, runs the n_layers Dense layers of
+ * `prepared` (rs_mlp_prepare on dims / the layers' kernels; acts[l] NONE /
+ * RELU / SIGMOID) and is normalised: out[b, :dims[n_layers]] = x *
+ * rsqrt(max(sum x^2, 1e-12)).  n_layers = 0 (an empty item_dnn_hidden_units,
+ * model/dssm.py:68-70) normalises the staged row (prepared may be NULL).
+ * Neither the concat nor an activation reaches HBM.  out is bit-identical to
+ * rs_concat_pieces + rs_seq_pool_fwd into a [B, dims[0]] buffer, rs_mlp_fwd
+ * (head 0), rs_l2_normalize_fwd — the same device functions — for any split
+ * of the batch.  rs_dssm_tower_ok(n_pieces + n_seq, n_layers, dims, acts): 1
+ * when the one-launch form takes the shape: 1..16 pieces, 0..8 layers, every
+ * width 1..1024, the rs_mlp_fwd tile within 160 KiB of LDS
+ * (rs_mlp_prepared_size >= 0), activations NONE / RELU / SIGMOID (a
+ * BatchNormalization, Dice or PReLU tower runs unfused in the host layer), and
+ * not the 256 -> 128 -> 64 -> 1 shape rs_mlp_fwd runs as its split-K tail.
+ * rs_l2_normalize_fwd: y[m, :N] = x[m] * rsqrt(max(sum_n x[m, n]^2, 1e-12)),
+ * one wave per row: lane l adds columns l, l + 64, ... ascending (fma), then a
+ * fixed butterfly over the wave.  In place allowed.
+ *
+ * rs_inbatch_softmax_fwd: user [B, E], item [B, E] (rows *_stride apart),
+ * item_idx [B] (RS_ID_I32 / RS_ID_I64), logq [n_items] = log(item_count /
+ * sum(item_count)):
+ *   z_ij = (u_i / temperature) . v_j - logq[item_idx[j]]
+ *   loss[i] = logsumexp_j z_ij - z_ii
+ * A workgroup owns 16 user rows; its 16 waves walk the item column tiles
+ * (wave w: tiles w, w + 16, ...) with v_mfma_f32_16x16x4_f32, K = E zero-padded
+ * to a multiple of 16, and keep a running (max, sum) per row; the partials
+ * merge in a fixed order (the 16 lanes of a row, then the waves in wave
+ * order), so the loss is bit-reproducible from run to run.  No [B, B] buffer
+ * and no workspace.  Columns past B are excluded; duplicated items are not
+ * masked (as the reference); an item_idx outside [0, n_items) uses logq = 0
+ * and sets *err_flag.  rs_inbatch_softmax_ok(E): 1 for 1 <= E <= 512.
+ * rs_dssm_score_fwd: out[b] = sigmoid((sum_k u_bk v_bk) / temperature), the
+ * 'logistic' head reduced over the last axis (the reference's
+ * tf.reduce_sum has no axis).
+ * All entries: stream-ordered, graph-capturable, no allocation; arguments are
+ * validated before any device work; nothing is launched for batch 0; every
+ * loop is bounded by an argument.                                           */
+int rs_seq_pool_fwd(int n_feat, const int* widths, const int* out_cols,
+                    const int* Ts, const int* combiners, const int* kinds,
+                    const void* const* srcs, const int64_t* src_strides,
+                    const float* const* tables, const int64_t* vocabs,
+                    const void* const* lengths, const int* len_kinds,
+                    const void* const* masks, float* out, int64_t out_stride,
+                    int64_t batch, int* err_flag, rs_stream_t stream);
+int rs_l2_normalize_fwd(const float* x, int64_t x_stride, float* y,
+                        int64_t y_stride, int64_t M, int N, rs_stream_t stream);
+int rs_dssm_tower_ok(int n_pieces, int n_layers, const int* dims,
+                     const int* acts);
+int rs_dssm_tower_fwd(int n_pieces, const int* widths, const int* in_cols,
+                      const int* kinds, const void* const* srcs,
+                      const int64_t* src_strides, const float* const* tables,
+                      const int64_t* vocabs, int n_seq, const int* seq_widths,
+                      const int* seq_cols, const int* seq_Ts,
+                      const int* combiners, const int* seq_kinds,
+                      const void* const* seq_srcs, const int64_t* seq_strides,
+                      const float* const* seq_tables,
+                      const int64_t* seq_vocabs, const void* const* lengths,
+                      const int* len_kinds, const void* const* masks,
+                      int n_layers, const int* dims, const int* acts,
+                      const float* prepared, float* out, int64_t out_stride,
+                      int64_t batch, int* err_flag, rs_stream_t stream);
+int rs_inbatch_softmax_ok(int E);
+int rs_inbatch_softmax_fwd(const float* user, int64_t user_stride,
+                           const float* item, int64_t item_stride,
+                           const void* item_idx, int idx_kind,
+                           const float* logq, int64_t n_items,
+                           float temperature, float* loss, int64_t batch, int E,
+                           int* err_flag, rs_stream_t stream);
+int rs_dssm_score_fwd(const float* user, int64_t user_stride,
+                      const float* item, int64_t item_stride,
+                      float temperature, float* out, int64_t batch, int E,
+                      rs_stream_t stream);
+
 /* ------------------------------------------ wide part of Wide&Deep (a17)
  * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
  * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense

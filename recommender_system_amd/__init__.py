@@ -11,9 +11,10 @@ from .layers import (AFMLayer, Attention, AttentionLayer, BatchNormalization, Cr
                      DNNLayer, EmbedLayer, FFMLayer, FGCNNLayer, FMLayer, InnerProductLayer, InteractionLayer,
                      OuterProductLayer, ResLayer, WideLayer, mmoe_layer, sigmoid_combine, tower_layer,
                      AUGRU, AUGRUCell, AttentionSequencePoolingLayer, DNN, GRU, InterestEvolution,
-                     LocalActivationUnit, PredictionLayer)
-from .models import AFM, DCN, DIEN, DIN, FFM, FM, MMOE, NFM, PNN, DeepCrossing, DeepFM, WideDeep  # noqa: F401
+                     LocalActivationUnit, PredictionLayer, InBatchSoftmaxLayer, SequencePoolingLayer)
+from .models import AFM, DCN, DIEN, DIN, DSSM, FFM, FM, MMOE, NFM, PNN, DeepCrossing, DeepFM, WideDeep  # noqa: F401
 from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, get_feature_names  # noqa: F401
+from .negative import NegativeSampler, recall_N, sampledsoftmaxloss  # noqa: F401
 from .dataset import create_criteo_dataset, denseFeature, features_dict, sparseFeature  # noqa: F401
 
 __version__ = "0.1.0"

@@ -108,6 +108,13 @@ SIGNATURES = {
     "rs_dien_prepare": (I, [I, P, P, P, P, P, I, P, I, P, P, P, P, P, P, P, P, P]),
     "rs_dien_evolution_fwd": (I, [P, L, L, P, L, P, I, I, I, I, P, I, I, I, P, P, P, P, L, L, P]),
     "rs_dien_evolution_ids_fwd": (I, [I, P, P, P, P, P, P, P, P, P, I, I, I, I, P, I, I, I, P, P, P, P, L, L, P, P]),
+    "rs_seq_pool_fwd": (I, [I, P, P, P, P, P, P, P, P, P, P, P, P, P, L, L, P, P]),
+    "rs_l2_normalize_fwd": (I, [P, L, P, L, L, I, P]),
+    "rs_dssm_tower_ok": (I, [I, I, P, P]),
+    "rs_dssm_tower_fwd": (I, [I, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, L, L, P, P]),
+    "rs_inbatch_softmax_ok": (I, [I]),
+    "rs_inbatch_softmax_fwd": (I, [P, L, P, L, P, I, P, L, F, P, L, I, P, P]),
+    "rs_dssm_score_fwd": (I, [P, L, P, L, F, P, L, I, P]),
     "rs_gru_prepared_size": (L, [I, I]),
     "rs_gru_prepare": (I, [I, I, P, P, P, P, P]),
     "rs_gru_fwd": (I, [P, L, L, I, I, I, P, P, P, L, L, P]),

@@ -258,7 +258,11 @@ __device__ __forceinline__ void mlp_mac(floatx4 (&ring)[MLP_R], const float* ap,
 // buf0 [16][rs] | buf1 [16][rs] | red [NW][256] | par [ptot] (loaded here).
 // l0 > 0: layers 0 .. l0-1 were computed by the caller (layer l0's input is
 // in buf (l0 & 1), its ring filled).
-template <int NW>
+// LAST_LDS (head 0 only): the last layer's tile is left in LDS, in buf
+// (a.L & 1) (rows RS apart, as a hidden layer's), instead of written to a.y —
+// the same values, for a caller that goes on with the tile (dssm.hip: the
+// row normalisation).  The caller takes the barrier before it reads.
+template <int NW, bool LAST_LDS = false>
 __device__ __forceinline__ void mlp_tower_tile(const MlpArgs& a, float* smem, int64_t m0, floatx4 (&ring)[MLP_R],
                                                const float* extra_lds = nullptr, int l0 = 0, int lstop = MLP_MAXL) {
   // layers l0 .. min(a.L, lstop) - 1 (lstop < a.L: a caller's split-K tail runs the rest)
@@ -295,7 +299,7 @@ __device__ __forceinline__ void mlp_tower_tile(const MlpArgs& a, float* smem, in
     // re-read after every store (the compiler cannot prove out != par)
     auto finish = [&](auto A, int row, int col, float v, float bc, float ac) {
       v = mlp_act_c<decltype(A)::value>(v + bc, ac);
-      if (!last) {
+      if (LAST_LDS || !last) {
         out[row * RS + col] = v;
       } else {
         const int64_t m = m0 + row;
@@ -385,7 +389,9 @@ __device__ __forceinline__ void mlp_tower_tile(const MlpArgs& a, float* smem, in
       const float* hb = par + a.poff[LH];
       float v = mlp_act(z + hb[0], a.act[LH], hb[a.Np[LH]]);
       const int64_t m = m0 + row;
-      if (m < a.M) {
+      if constexpr (LAST_LDS) {
+        out[row * RS] = v;  // (out: the head layer's output buffer, buf (a.L & 1))
+      } else if (m < a.M) {
         if (a.head == 0) {
           a.y[m * a.ys] = v;
         } else {

@@ -28,6 +28,9 @@ Each class keeps the reference layer's name, constructor arguments and
   DNN(hidden_units, activation, use_bn, ...)  layer/core.py:123-205
   PredictionLayer(task, use_bias)             layer/core.py:223-256
   InterestEvolution(embedding_size, ...)      model/dien.py:54-80 (interest_evolution)
+  SequencePoolingLayer(mode, supports_masking) layer/sequence.py:20-95
+  InBatchSoftmaxLayer(sampler_config, temperature)
+                                              layer/activation.py:267-285
   Dense / PReLU / BatchNormalization          the Keras layers the models use
 
 Weights are built lazily on the first call from the input shape, like Keras
@@ -2254,3 +2257,144 @@ class PredictionLayer(KerasModule):
             call("rs_affine_act", ptr(x), 1, ptr(self._one), ptr(self.global_bias if self.use_bias else self._zero),
                  None, _lib.ACT["sigmoid"] if self.task == "binary" else 0, ptr(out), 1, x.shape[0], 1, _stream())
         return out
+
+
+# ------------------------------------------------------------------- DSSM
+_COMBINERS = {"sum": 0, "mean": 1, "max": 2}
+_SEQ_MAXF, _SEQ_MAXE = 8, 256  # rs_seq_pool_fwd limits (dssm.hip)
+
+
+def seq_pool_ok(E):
+    """Widths rs_seq_pool_fwd takes: 1..64, or a multiple of 4 up to 256."""
+    return E >= 1 and (E <= 64 or (E % 4 == 0 and E <= _SEQ_MAXE))
+
+
+def seq_pool_arrays(feats):
+    """The thirteen per-feature host arrays of rs_seq_pool_fwd (and of the
+    sequence pieces of rs_dssm_tower_fwd) for feats = [(E, column, T, combiner,
+    source, table or None, lengths or None, mask or None)]: source = ids [B, T]
+    with a table, embedded values [B, T, E] without."""
+    n = len(feats)
+    ci = lambda v: (C.c_int * n)(*v)
+    cp = lambda v: (C.c_void_p * n)(*v)
+    cl = lambda v: (C.c_int64 * n)(*v)
+    kinds = [-1 if f[5] is None else _lib.id_kind(f[4]) for f in feats]
+    return (ci([f[0] for f in feats]), ci([f[1] for f in feats]), ci([f[2] for f in feats]),
+            ci([_COMBINERS[f[3]] for f in feats]), ci(kinds), cp([ptr(f[4]) for f in feats]),
+            cl([f[4].stride(0) for f in feats]), cp([ptr(f[5]) for f in feats]),
+            cl([0 if f[5] is None else f[5].shape[0] for f in feats]), cp([ptr(f[6]) for f in feats]),
+            ci([0 if f[6] is None else _lib.id_kind(f[6]) for f in feats]), cp([ptr(f[7]) for f in feats]))
+
+
+def seq_pool(feats, out, B, err):
+    """rs_seq_pool_fwd over feats (seq_pool_arrays) into out [B, *], 8 features a launch."""
+    for i in range(0, len(feats) if B else 0, _SEQ_MAXF):
+        ch = feats[i:i + _SEQ_MAXF]
+        call("rs_seq_pool_fwd", len(ch), *seq_pool_arrays(ch), ptr(out), out.stride(0), B, ptr(err.t), _stream())
+
+
+def l2_normalize(x, out=None):
+    """tf.math.l2_normalize(x, axis=-1) of x [M, N]: rs_l2_normalize_fwd."""
+    if out is None:
+        out = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
+    call("rs_l2_normalize_fwd", ptr(x), x.stride(0), ptr(out), out.stride(0), x.shape[0], x.shape[1], _stream())
+    return out
+
+
+class SequencePoolingLayer(KerasModule):
+    """SequencePoolingLayer(mode='mean', supports_masking=False) —
+    layer/sequence.py:20-95: sum / mean / max pooling of a variable-length
+    sequence, one rs_seq_pool_fwd launch.  ``forward([seq_value [B, T, E],
+    seq_len [B] or [B, 1]])``, or with ``supports_masking=True``
+    ``forward(seq_value, mask=[B, T] bool)``; returns [B, 1, E].
+    ``forward_ids(ids [B, T], table [vocab, E], lengths=None, out=None)`` pools
+    straight from the ids — masked rows are never loaded — and returns [B, E];
+    ``lengths=None`` is the reference's mask_zero form (mask = id != 0)."""
+
+    def __init__(self, mode="mean", supports_masking=False, device=None):
+        super().__init__(device)
+        if mode not in ("sum", "mean", "max"):
+            raise ValueError("mode must be sum or mean")
+        self.mode, self.supports_masking = mode, bool(supports_masking)
+
+    def _run(self, feat, B, E, out, check_ids, what):
+        if not seq_pool_ok(E):
+            raise _lib.RSError(f"{what}: width {E} not supported (1..64, or a multiple of 4 up to {_SEQ_MAXE})")
+        if out is None:
+            out = torch.empty(B, E, dtype=torch.float32, device=self._dev)
+        err = _ErrFlag(self._dev)
+        seq_pool([(E, 0, feat[0], self.mode) + feat[1:]], out, B, err)
+        if check_ids:
+            err.check(what)
+        return out
+
+    def forward(self, seq_value_len_list, mask=None):
+        if self.supports_masking:
+            if mask is None:
+                raise ValueError("When supports_masking=True,input must support masking")
+            x = _seq_input(seq_value_len_list, self._dev, "SequencePoolingLayer").contiguous()
+            m = torch.as_tensor(mask).to(self._dev).reshape(x.shape[0], x.shape[1]).ne(0).contiguous()
+            L = None
+        else:
+            x, L = seq_value_len_list
+            x = _seq_input(x, self._dev, "SequencePoolingLayer").contiguous()
+            L, m = _lengths(L, self._dev, x.shape[0]), None
+        B, T, E = x.shape
+        return self._run((T, x, None, L, m), B, E, None, False, "SequencePoolingLayer").unsqueeze(1)
+
+    def forward_ids(self, ids, table, lengths=None, out=None, check_ids=True):
+        ids = _ids_tensor(ids, self._dev).contiguous()
+        if ids.dim() != 2:
+            raise ValueError(f"SequencePoolingLayer.forward_ids: ids must be [batch, T], got {tuple(ids.shape)}")
+        B, T = ids.shape
+        L = None if lengths is None else _lengths(lengths, self._dev, B)
+        return self._run((T, ids, table, L, None), B, table.shape[1], out, check_ids,
+                         "SequencePoolingLayer.forward_ids")
+
+
+class InBatchSoftmaxLayer(KerasModule):
+    """InBatchSoftmaxLayer(sampler_config, temperature=1.0) —
+    layer/activation.py:267-285 with layer/utils.py:206-215:
+    ``forward([user_vec [B, E], item_vec [B, E], item_idx [B] or [B, 1]])``
+    returns the per-sample loss [B, 1],
+        logits = (user / temperature) @ item^T - log Q[item_idx]   (per column)
+        loss_i = logsumexp_j logits_ij - logits_ii
+    in one rs_inbatch_softmax_fwd launch — the [B, B] logits are never written.
+    ``sampler_config``: a NegativeSampler or its ``_asdict()``; log Q is built
+    once, as the reference builds it: float32(item_count / sum(item_count))
+    (divided in float64), then a float32 log.  A width the kernel refuses
+    (rs_inbatch_softmax_ok) runs the same composition in torch ops."""
+
+    def __init__(self, sampler_config, temperature=1.0, device=None):
+        super().__init__(device)
+        import numpy as np
+        cfg = sampler_config._asdict() if hasattr(sampler_config, "_asdict") else dict(sampler_config)
+        self.sampler_config, self.temperature = cfg, float(temperature)
+        self.item_count = cfg["item_count"]
+        if self.item_count is None:
+            raise ValueError(" `item_count` must not be `None` when using `inbatch` or `frequency` sampler")
+        q = (np.asarray(self.item_count) / np.sum(self.item_count)).astype(np.float32)
+        with np.errstate(divide="ignore"):
+            self.logq = torch.from_numpy(np.log(q)).to(self._dev)
+
+    def forward(self, inputs_with_item_idx, check_ids=True):
+        u, v, idx = inputs_with_item_idx
+        u, v = _to_device_f32(u, self._dev), _to_device_f32(v, self._dev)
+        idx = torch.as_tensor(idx)
+        if idx.dtype not in (torch.int32, torch.int64):
+            idx = idx.to(torch.int64)
+        idx = idx.to(self._dev).reshape(-1).contiguous()
+        B, E = u.shape
+        if v.shape != u.shape or idx.numel() != B:
+            raise ValueError(f"InBatchSoftmaxLayer: user {tuple(u.shape)}, item {tuple(v.shape)}, "
+                             f"{idx.numel()} item indices")
+        if not _lib.lib().rs_inbatch_softmax_ok(E):
+            z = (u / self.temperature) @ v.t() - self.logq[idx.long()].unsqueeze(0)
+            return (torch.logsumexp(z, dim=1) - torch.diagonal(z)).unsqueeze(1)
+        loss = torch.empty(B, 1, dtype=torch.float32, device=self._dev)
+        err = _ErrFlag(self._dev)
+        call("rs_inbatch_softmax_fwd", ptr(u), u.stride(0), ptr(v), v.stride(0), ptr(idx), _lib.id_kind(idx),
+             ptr(self.logq), self.logq.numel(), self.temperature, ptr(loss), B, E, ptr(err.t), _stream())
+        if check_ids:
+            err.check("InBatchSoftmaxLayer")
+        return loss

@@ -23,6 +23,7 @@ models (Hcyand/recommender_system, algorithm/deep_learning/model/):
        activation='relu', use_expert_bias=True, use_gate_bias=True) model/mmoe.py:10-32
   DIEN(dnn_feature_columns, history_feature_list, gru_type='GRU', ...)
                                                                   model/dien.py:83-169
+  DSSM(user_feature_columns, item_feature_columns, ...)           model/dssm.py:17-90 (dssm.py)
 
 Criteo-style models take the reference's packed input X[B, 13+F] (dense
 features followed by label-encoded sparse ids, as floats — Keras casts them to
@@ -2219,3 +2220,6 @@ class DIEN(TowerMixin, KerasModule):
             self._table_sgd(self.tables[c.embedding_name], self._ids(inputs, c, True), gr.contiguous(), lr, st)
         self._weights_changed()
         return loss
+
+
+from .dssm import DSSM  # noqa: E402,F401  (the two-tower retrieval model: dssm.py)
