@@ -1104,6 +1104,96 @@ int rs_dssm_score_fwd(const float* user, int64_t user_stride,
                       float temperature, float* out, int64_t batch, int E,
                       rs_stream_t stream);
 
+/* ------------------------------------------------- DSSM training (a31)
+ * One step of Keras fit on model/dssm.py:149-152 (optimizer "adam", loss
+ * sampledsoftmaxloss = the batch mean of the in-batch softmax losses).
+ *
+ * rs_inbatch_softmax_train_fwd: rs_inbatch_softmax_fwd that also writes
+ * lse[i] = logsumexp_j z_ij.  The same device function walks the tiles, so
+ * loss is bit-identical to rs_inbatch_softmax_fwd's.
+ *
+ * rs_inbatch_softmax_bwd: with p_ij = exp(z_ij - lse_i) and
+ * dz_ij = g_i (p_ij - [i == j]) (g = NULL: g_i = 1 / B; logq is a constant;
+ * duplicated items are not masked),
+ *   du[i] = (1 / temperature) sum_j dz_ij v_j
+ *   dv[j] = sum_i dz_ij (u_i / temperature)
+ * Two launches of one kernel.  A workgroup owns 16 user rows (du) or 16 item
+ * rows (dv); its 8 waves walk the other side's 16-row tiles (wave w: tiles w,
+ * w + 8, ...): the logits tile is recomputed with v_mfma_f32_16x16x4_f32 with
+ * the OTHER side on the accumulator's rows (du recomputes z^T, dv z), dz is
+ * formed in those registers and is the B operand of the second MFMA product
+ * as it stands; K = E zero-padded to a multiple of 16.  Sum order: within a
+ * wave its tiles ascending (inside a tile the MFMA's k order), then the
+ * waves' partial tiles in wave order — no [B, B] buffer, no atomics, du and dv
+ * bit-identical from run to run.  An item_idx outside [0, n_items) uses
+ * logq = 0 and sets *err_flag.  rs_inbatch_softmax_bwd_ok(E): 1 for
+ * 1 <= E <= 256 (nine 16-row tiles of E + 4 floats in the 160 KiB of LDS;
+ * the E / 4 accumulator registers per lane would allow 512).
+ *
+ * rs_l2_normalize_bwd: for y = x r, r = rsqrt(max(s, 1e-12)), s = sum x^2:
+ * dx = r (dy - y (y . dy)) where s >= 1e-12, r dy (= 1e6 dy) below.  One wave
+ * per row; s and y . dy are the forward's sums: lane l adds columns l, l + 64,
+ * ... ascending (fma), then the fixed butterfly.  dx may alias dy.
+ *
+ * rs_embedding_grad_accum: G[id(b, t), 0:k] += scale_b grad[b, 0:k] for every
+ * valid position of ids [B, T] (rows id_stride apart), G dense [n_rows, k].
+ * combiner -1: every position is valid and scale_b = 1 (T = 1: a SparseFeat
+ * column); 0 (sum) / 1 (mean): rs_seq_pool_fwd's validity — t < lengths[b]
+ * (int32 / int64; a length above T keeps all T, <= 0 none) or, with lengths
+ * NULL, id != 0 — and scale_b = 1 or 1 / (float(len_b) + 1e-8), len_b the
+ * length input or the count of non-zero ids, computed on the device.  The
+ * lookups are sorted by row (stable radix sort), a row's duplicates are summed
+ * in lookup order (b, t) ascending (chunked segment sums, as
+ * rs_embedding_sgd_strided) and added to G once; the gradient row is read
+ * through the sorted position, so no [B, T, k] buffer exists.  An id outside
+ * [0, n_rows) at a valid position sets *err_flag and contributes nothing.
+ * workspace: rs_embedding_grad_accum_workspace_size(batch * T) bytes.
+ *
+ * rs_adam_update_multi: Keras optimizer_v2 Adam over count tensors, 32 per
+ * launch: with t = *step + 1 (step: int64 in device memory, so a captured
+ * step replays correctly), g = grad + 2 l2 w,
+ *   lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)   (float; 1 - beta^t as
+ *                                        -expm1(t log beta))
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   w -= lr_t m / (sqrt(v) + eps)
+ * beta1 / beta2 are the float32 values Keras' own variables hold; 1 - beta and
+ * log beta are formed from them in double and rounded once.  rs_adam_advance: *step += 1 on the stream (after the last
+ * rs_adam_update_multi of the step).
+ * All entries: stream-ordered, graph-capturable, no allocation; arguments are
+ * validated before any device work; nothing is launched for batch 0; every
+ * loop is bounded by an argument.                                           */
+int rs_inbatch_softmax_train_fwd(const float* user, int64_t user_stride,
+                                 const float* item, int64_t item_stride,
+                                 const void* item_idx, int idx_kind,
+                                 const float* logq, int64_t n_items,
+                                 float temperature, float* loss, float* lse,
+                                 int64_t batch, int E, int* err_flag,
+                                 rs_stream_t stream);
+int rs_inbatch_softmax_bwd_ok(int E);
+int rs_inbatch_softmax_bwd(const float* user, int64_t user_stride,
+                           const float* item, int64_t item_stride,
+                           const void* item_idx, int idx_kind,
+                           const float* logq, int64_t n_items,
+                           float temperature, const float* lse, const float* g,
+                           float* du, int64_t du_stride, float* dv,
+                           int64_t dv_stride, int64_t batch, int E,
+                           int* err_flag, rs_stream_t stream);
+int rs_l2_normalize_bwd(const float* x, int64_t x_stride, const float* dy,
+                        int64_t dy_stride, float* dx, int64_t dx_stride,
+                        int64_t M, int N, rs_stream_t stream);
+int64_t rs_embedding_grad_accum_workspace_size(int64_t n_lookups);
+int rs_embedding_grad_accum(float* G, int64_t n_rows, int k, const void* ids,
+                            int id_kind, int64_t id_stride, int T,
+                            const void* lengths, int len_kind, int combiner,
+                            const float* grad, int64_t grad_stride,
+                            int64_t batch, void* workspace, int* err_flag,
+                            rs_stream_t stream);
+int rs_adam_update_multi(int count, float* const* w, const float* const* grad,
+                         float* const* m, float* const* v, const int64_t* n,
+                         const float* l2, float lr, float beta1, float beta2,
+                         float eps, const int64_t* step, rs_stream_t stream);
+int rs_adam_advance(int64_t* step, rs_stream_t stream);
+
 /* ------------------------------------------ wide part of Wide&Deep (a17)
  * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
  * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense

@@ -6,7 +6,7 @@ DIN attention), as hand-written gfx950 HIP kernels behind a C-ABI
 (include/rs_capi.h, librs_hip.so) with a Python host layer that keeps the
 reference's Keras layer / model names and signatures.
 """
-from . import _lib  # noqa: F401
+from . import _lib, optim  # noqa: F401
 from .layers import (AFMLayer, Attention, AttentionLayer, BatchNormalization, CrossLayer, Dense, Dice,  # noqa: F401
                      DNNLayer, EmbedLayer, FFMLayer, FGCNNLayer, FMLayer, InnerProductLayer, InteractionLayer,
                      OuterProductLayer, ResLayer, WideLayer, mmoe_layer, sigmoid_combine, tower_layer,

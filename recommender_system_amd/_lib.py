@@ -115,6 +115,14 @@ SIGNATURES = {
     "rs_inbatch_softmax_ok": (I, [I]),
     "rs_inbatch_softmax_fwd": (I, [P, L, P, L, P, I, P, L, F, P, L, I, P, P]),
     "rs_dssm_score_fwd": (I, [P, L, P, L, F, P, L, I, P]),
+    "rs_inbatch_softmax_train_fwd": (I, [P, L, P, L, P, I, P, L, F, P, P, L, I, P, P]),
+    "rs_inbatch_softmax_bwd_ok": (I, [I]),
+    "rs_inbatch_softmax_bwd": (I, [P, L, P, L, P, I, P, L, F, P, P, P, L, P, L, L, I, P, P]),
+    "rs_l2_normalize_bwd": (I, [P, L, P, L, P, L, L, I, P]),
+    "rs_embedding_grad_accum_workspace_size": (L, [L]),
+    "rs_embedding_grad_accum": (I, [P, L, I, P, I, L, I, P, I, I, P, L, L, P, P, P]),
+    "rs_adam_update_multi": (I, [I, P, P, P, P, P, P, F, F, F, F, P, P]),
+    "rs_adam_advance": (I, [P, P]),
     "rs_gru_prepared_size": (L, [I, I]),
     "rs_gru_prepare": (I, [I, I, P, P, P, P, P]),
     "rs_gru_fwd": (I, [P, L, L, I, I, I, P, P, P, L, L, P]),

@@ -1,14 +1,14 @@
 """DSSM — the reference's two-tower retrieval model (model/dssm.py:17-90),
-forward.  ``models.DSSM`` is this class."""
+forward and training step.  ``models.DSSM`` is this class."""
 from __future__ import annotations
 
 import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, _train_ops
 from ._lib import call, ptr
-from ._train_ops import _subseed
+from ._train_ops import _dropout_rng, _subseed, bce_head_logit, bn_train_bwd, bn_train_fwd, gemm_ws, scratch
 from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, build_input_features
 from .layers import (DNN, InBatchSoftmaxLayer, KerasModule, TowerMixin, _ErrFlag, _ids_tensor, _lengths,
                      _to_device_f32, l2_normalize, seq_pool, seq_pool_arrays, seq_pool_ok, _SEQ_MAXF)
@@ -75,7 +75,9 @@ class DSSM(KerasModule):
     user_dnn_hidden_units=(64, 32), item_dnn_hidden_units=(64, 32),
     dnn_activation='relu', dnn_use_bn=False, l2_reg_dnn=0, l2_reg_embedding=1e-6,
     dnn_dropout=0, loss_type='softmax', temperature=0.05, sampler_config=None,
-    seed=1024) — model/dssm.py:17-90, forward only.
+    seed=1024) — model/dssm.py:17-90, forward and one step of its Keras fit
+    (``gradients`` / ``train_step`` / ``fit``: Adam on the batch mean of the
+    in-batch softmax losses, model/dssm.py:149-152).
 
     ``forward(inputs)`` takes the dict gen_model_input builds (name -> array,
     utils/inputs.py:204-209) and returns, for ``loss_type='softmax'``, the
@@ -102,7 +104,7 @@ class DSSM(KerasModule):
     Deviation: the reference's inner_product calls
     tf.reduce_sum without an axis, which collapses the whole batch to one
     scalar; 'logistic' here reduces over the last axis and returns [B, 1].
-    l2 / dropout are training-only; training (Adam) is not built.
+    l2 / dropout are training-only (``train_step``).
 
     Keras weight names (``keras_weights`` / ``set_keras_weights`` round-trip):
     ``sparse_emb_{embedding_name}/embeddings`` or, when a var-len column shares
@@ -268,3 +270,240 @@ class DSSM(KerasModule):
         rs_seq_pool_fwd into a [B, width] buffer, rs_mlp_fwd (DNN.forward for a
         tower it does not take), rs_l2_normalize_fwd."""
         return self._forward(inputs, check_ids, False)
+
+    # ---- training
+    _TRAIN_ACTS = (None, "linear", "relu", "sigmoid")
+
+    def _check_train(self, labels):
+        for tw in (self.user_tower, self.item_tower):
+            if any(l.activation not in self._TRAIN_ACTS for l in tw.dnn.layers):
+                raise NotImplementedError("DSSM: training takes 'relu' / 'sigmoid' / linear tower layers only")
+        if self.loss_type == "logistic" and labels is None:
+            raise ValueError("DSSM: loss_type 'logistic' needs labels to train")
+
+    def _tower_train_fwd(self, tw, x, dt, drop, st):
+        """DNN(..., output_activation='linear') in training mode on x [B, width]:
+        Dense, BatchNormalization on the batch's statistics, the activation,
+        the Dropout draw (layer/core.py:187-205).  Returns what _tower_train_bwd
+        reads; ctx["out"] is the tower's output."""
+        dnn, B = tw.dnn, x.shape[0]
+        ctx = {"in": [x], "pre": [], "bn": [], "saved": [], "act": [], "offs": []}
+        for i, l in enumerate(dnn.layers):
+            z = dt.dense(ctx["in"][-1], l, B)
+            bn_saved = None
+            if dnn.use_bn:
+                ctx["bn"].append(z)
+                bn_saved, z = bn_train_fwd(dnn.bn_layers[i], z, st)
+            saved, y = (None, z) if l.activation in (None, "linear") else dt.act_fwd(l, z, B)
+            ctx["pre"].append(z), ctx["saved"].append((bn_saved, saved)), ctx["act"].append(y)
+            if drop is not None:
+                y = y.clone()  # (the activation's backward reads its undropped output)
+                ctx["offs"].append(drop[0].draw(y, drop[1], st))
+            ctx["in"].append(y)
+        ctx["out"] = ctx["in"][-1]
+        return ctx
+
+    def _tower_train_bwd(self, tw, ctx, dh, dt, drop, st):
+        """dL/d(input row) from dh = dL/d(tower output); the layers' gradients go to dt.updates."""
+        dnn, B = tw.dnn, dh.shape[0]
+        for i in reversed(range(len(dnn.layers))):
+            l = dnn.layers[i]
+            if drop is not None:  # the forward's mask, regenerated from its offset
+                dh = dh.contiguous()
+                drop[0].redraw(dh, drop[1], ctx["offs"][i], st)
+            dz = dh if l.activation in (None, "linear") else \
+                dt.act_bwd(l, ctx["pre"][i], ctx["act"][i], ctx["saved"][i][1], dh, B)
+            if dnn.use_bn:
+                bn = dnn.bn_layers[i]
+                dz, dgam, dbet = bn_train_bwd(bn, ctx["bn"][i], ctx["saved"][i][0], dz.contiguous(), st)
+                dt.updates.extend([(bn.gamma, dgam, 0.0), (bn.beta, dbet, 0.0)])
+            dh = dt.dense_bwd(l, ctx["in"][i], dz, l2=float(dnn.l2_reg or 0))
+        return dh
+
+    def _grad_accum(self, G, ids, T, lengths, combiner, grad_ptr, grad_stride, B, err, st):
+        """rs_embedding_grad_accum of one id source into the dense table gradient G."""
+        ws = scratch(self, "_ega_ws", _lib.lib().rs_embedding_grad_accum_workspace_size(B * T))
+        call("rs_embedding_grad_accum", ptr(G), G.shape[0], G.shape[1], ptr(ids), _lib.id_kind(ids),
+             ids.stride(0) if ids.dim() == 2 else 1, T, ptr(lengths), 0 if lengths is None else _lib.id_kind(lengths),
+             combiner, grad_ptr, grad_stride, B, ptr(ws), ptr(err.t), st)
+
+    def _table_grads(self, sources, B, err, st):
+        """One zero-fill per table, then one rs_embedding_grad_accum per id
+        source in a fixed order: user columns, then item columns, each in
+        input-row order.  A 'max' column (its gradient goes to the positions
+        that hold the maximum, a tie split evenly as TF's reduce_max does) is
+        composed in torch and added through the same entry."""
+        name_of = {id(t): en for en, t in self.tables.items()}
+        G = self.__dict__.setdefault("_table_grad_bufs", {})
+        for en, t in self.tables.items():
+            if en not in G or G[en].shape != t.shape:
+                G[en] = torch.empty_like(t)
+            G[en].zero_()
+        for (pieces, seqs), dx in sources:
+            for width, at, ids, table in pieces:
+                if table is not None:
+                    self._grad_accum(G[name_of[id(table)]], ids, 1, None, -1, dx.data_ptr() + 4 * at, dx.stride(0), B,
+                                     err, st)
+            for E, at, T, comb, ids, table, L, _ in seqs:
+                g = G[name_of[id(table)]]
+                if comb != "max":
+                    self._grad_accum(g, ids, T, L, {"sum": 0, "mean": 1}[comb], dx.data_ptr() + 4 * at, dx.stride(0), B, err,
+                                     st)
+                    continue
+                valid = (torch.arange(T, device=self._dev).unsqueeze(0) < L.unsqueeze(1)) if L is not None \
+                    else ids.ne(0)
+                rows = table[ids.long().clamp(0, table.shape[0] - 1)] - (~valid).unsqueeze(-1) * 1e9
+                tie = (rows == rows.max(1, keepdim=True).values).to(torch.float32)
+                gr = (tie / tie.sum(1, keepdim=True) * dx[:, at:at + E].unsqueeze(1)).reshape(B * T, E).contiguous()
+                self._grad_accum(g, ids.reshape(B * T), 1, None, -1, gr.data_ptr(), E, B * T, err, st)
+        return G
+
+    def gradients(self, inputs, labels=None, check_ids=True, dropout=None):
+        """(grads, losses) of one training batch: ``grads`` maps the Keras name
+        of every trainable weight (``keras_weights()`` without the moving
+        statistics) to the gradient of the DATA loss — the batch mean of the
+        per-sample losses; tables dense [vocab, E] with exact zeros in rows
+        nobody looked up; no regulariser — and ``losses`` is the per-sample
+        [B, 1] before the step (the in-batch softmax loss, or the BCE of
+        sigmoid(u . v / temperature) against ``labels`` for 'logistic').  No
+        weight changes except BatchNormalization's moving statistics.
+        The table gradients live in buffers the model keeps: they hold until
+        the next call.
+
+        Order: the tower inputs (rs_concat_pieces + rs_seq_pool_fwd) and the
+        id check; each tower in training mode (rs_dense_fwd, rs_bn_train_fwd,
+        the dropout draws, as DIEN's tower); rs_l2_normalize_fwd,
+        rs_inbatch_softmax_train_fwd, rs_inbatch_softmax_bwd (an embedding
+        wider than rs_inbatch_softmax_bwd_ok: the same math in torch ops),
+        rs_l2_normalize_bwd; the towers backward; rs_embedding_grad_accum per
+        id source.  ``dropout``: None applies dnn_dropout, False turns it off,
+        a float overrides the rate."""
+        self._check_train(labels)
+        dev, st = self._dev, _lib.stream()
+        towers = (self.user_tower, self.item_tower)
+        rate = [0.0 if dropout is False else float(tw.dnn.dropout_rate or 0) if dropout is None or dropout is True
+                else float(dropout) for tw in towers]
+        # ---- inputs: every id is checked before anything else is touched
+        err = _ErrFlag(dev)
+        src = [self._pieces(tw, inputs) for tw in towers]
+        B = src[0][2]
+        if src[1][2] != B:
+            raise ValueError(f"DSSM: the inputs hold {B} and {src[1][2]} samples")
+        if not B:
+            raise ValueError("DSSM: an empty batch")
+        xs = [self._tower_input(tw, p, s, B, err) for tw, (p, s, _) in zip(towers, src)]
+        idx = None
+        if self.loss_type == "softmax":
+            idx = torch.as_tensor(inputs[self.sampler_config.item_name])
+            if idx.dtype not in (torch.int32, torch.int64):
+                idx = idx.to(torch.int64)
+            idx = idx.to(dev).reshape(-1).contiguous()
+            if check_ids and bool(((idx < 0) | (idx >= self.softmax.logq.numel())).any()):
+                raise _lib.BadIdError("DSSM: item index out of range of sampler_config.item_count")
+        if check_ids:
+            err.check("DSSM")
+        shapes = [(l.kernel.shape[0], l.kernel.shape[1], B) for tw in towers for l in tw.dnn.layers] or [(1, 1, B)]
+        dt = _train_ops.DenseTrain(gemm_ws(self, _train_ops.dense_train_need(shapes)), st, dev)
+        emp = dt.emp
+
+        # ---- forward
+        drops = [(_dropout_rng(self), r, None) if r > 0 else None for r in rate]
+        ctx = [self._tower_train_fwd(tw, x, dt, d, st) for tw, x, d in zip(towers, xs, drops)]
+        yu, yv = (c["out"].contiguous() for c in ctx)
+        u, v = l2_normalize(yu), l2_normalize(yv)
+        E = u.shape[1]
+        if self.loss_type == "softmax":
+            logq, temp = self.softmax.logq, self.temperature
+            if _lib.lib().rs_inbatch_softmax_bwd_ok(E):
+                losses, lse, du, dv = emp(B, 1), emp(B), emp(B, E), emp(B, E)
+                head = (ptr(u), E, ptr(v), E, ptr(idx), _lib.id_kind(idx), ptr(logq), logq.numel(), temp)
+                call("rs_inbatch_softmax_train_fwd", *head, ptr(losses), ptr(lse), B, E, ptr(err.t), st)
+                call("rs_inbatch_softmax_bwd", *head, ptr(lse), None, ptr(du), E, ptr(dv), E, B, E, ptr(err.t), st)
+            else:
+                z = (u / temp) @ v.t() - logq[idx.long()].unsqueeze(0)
+                lse = torch.logsumexp(z, dim=1)
+                losses = (lse - torch.diagonal(z)).unsqueeze(1)
+                dz = (torch.exp(z - lse.unsqueeze(1)) - torch.eye(B, device=dev)) / B
+                du, dv = (dz @ v) / temp, dz.t() @ (u / temp)
+        else:
+            t = _to_device_f32(labels, dev).reshape(-1)
+            if t.numel() != B:
+                raise ValueError(f"DSSM: {t.numel()} labels for a batch of {B}")
+            g, loss = bce_head_logit(((u * v).sum(1) / self.temperature).contiguous(), t, True, st)
+            losses = loss.unsqueeze(1)
+            du, dv = g.unsqueeze(1) * v / self.temperature, g.unsqueeze(1) * u / self.temperature
+            du, dv = du.contiguous(), dv.contiguous()
+
+        # ---- backward
+        dxs = []
+        for tw, c, y, d, drop in zip(towers, ctx, (yu, yv), (du, dv), drops):
+            call("rs_l2_normalize_bwd", ptr(y), y.stride(0), ptr(d), d.stride(0), ptr(d), d.stride(0), B, E, st)
+            dxs.append(self._tower_train_bwd(tw, c, d, dt, drop, st).contiguous())
+        if any(d is not None for d in drops):
+            _dropout_rng(self).end_step(st)
+        G = self._table_grads([((p, s), dx) for (p, s, _), dx in zip(src, dxs)], B, err, st)
+        by_param = {id(w): g for w, g, _ in dt.updates}
+        grads = {}
+        for name, p in self.keras_weights().items():
+            if name.endswith("/embeddings"):
+                en = next(e for e, kn in self._table_names.items() if f"{kn}/embeddings" == name)
+                grads[name] = G[en]
+            elif id(p) in by_param:
+                grads[name] = by_param[id(p)]
+        self._weights_changed()  # (the moving statistics moved)
+        return grads, losses
+
+    def _l2_of(self, name):
+        if name.endswith("/embeddings"):
+            return float(self.l2_reg_embedding or 0)
+        if name.rsplit("/", 1)[-1].startswith("kernel"):
+            tw = self.item_tower if name.startswith("dnn_1/") else self.user_tower
+            return float(tw.dnn.l2_reg or 0)
+        return 0.0
+
+    def optimizer(self, lr=0.001):
+        """The model's Adam (optim.Adam), created on first use."""
+        opt = self.__dict__.get("_adam")
+        if opt is None:
+            from .optim import Adam
+            opt = self.__dict__["_adam"] = Adam(lr=lr, device=self._dev)
+        return opt
+
+    def train_step(self, inputs, labels=None, lr=0.001, return_loss=False, check_ids=True, dropout=None):
+        """One step of Keras fit (model/dssm.py:149-152: Adam, lr 0.001, on the
+        batch mean of the per-sample losses): exactly ``gradients`` followed by
+        one ``Adam.apply`` over every trainable weight, with l2_reg_embedding
+        on the whole tables and l2_reg_dnn on the tower kernels folded into
+        the optimizer entry (gradient + 2 l2 w).  Adam is applied to every row
+        of every table each step, as Keras does: the tables' regulariser makes
+        their gradient dense, and Keras' non-lazy sparse Adam decays the moments
+        of untouched rows even without it.  Every id is checked before any
+        weight changes.  A 'max'-pooled column raises NotImplementedError.
+        Returns the per-sample losses [B, 1] before the step when
+        ``return_loss``."""
+        for tw in (self.user_tower, self.item_tower):
+            if any(c.combiner == "max" for c in tw.varlen_cols):
+                raise NotImplementedError("DSSM.train_step: 'max' pooling is not built (sum / mean only)")
+        self._check_train(labels)
+        opt = self.optimizer(lr)
+        grads, losses = self.gradients(inputs, labels, check_ids=check_ids, dropout=dropout)
+        own = self.keras_weights()
+        opt.apply([(own[name], g, self._l2_of(name)) for name, g in grads.items()], _lib.stream(), lr=lr)
+        self._weights_changed()
+        return losses if return_loss else None
+
+    def fit(self, inputs, labels=None, batch_size=256, epochs=1, lr=0.001):
+        """``train_step`` over sequential batches of ``batch_size`` (the last
+        one short), ``epochs`` times; returns the mean per-sample loss of each
+        epoch.  Deviation: Keras' fit shuffles the samples every epoch, this
+        keeps their order."""
+        n, batch_size = len(next(iter(inputs.values()))), int(batch_size)
+        history = []
+        for _ in range(int(epochs)):
+            total = torch.zeros((), dtype=torch.float64, device=self._dev)
+            for i in range(0, n, batch_size):
+                xb = {k: v[i:i + batch_size] for k, v in inputs.items()}
+                lb = None if labels is None else labels[i:i + batch_size]
+                total += self.train_step(xb, lb, lr=lr, return_loss=True).sum(dtype=torch.float64)
+            history.append(float(total) / n)
+        return history

@@ -43,9 +43,10 @@ VOCAB = dict(user_id=6041, gender=3, age=8, occupation=22, zip=3440, movie_id=37
 PROFILE = ("user_id", "gender", "age", "occupation", "zip")
 
 
-def runner(fn):
-    """fn replayed REPS times from a captured graph ('graph'), or called REPS
-    times ('eager') when the capture fails."""
+def runner(fn, reps=None):
+    """fn replayed reps (default REPS) times from a captured graph ('graph'),
+    or called reps times ('eager') when the capture fails."""
+    reps = REPS if reps is None else int(reps)
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -57,7 +58,7 @@ def runner(fn):
             fn()
             torch.cuda.synchronize()
             with torch.cuda.graph(g, stream=s):
-                for _ in range(REPS):
+                for _ in range(reps):
                     fn()
         torch.cuda.synchronize()
         return g.replay, "graph"
@@ -66,7 +67,7 @@ def runner(fn):
         print(f"capture failed ({type(ex).__name__}: {ex}); eager timing", file=sys.stderr)
 
         def eager():
-            for _ in range(REPS):
+            for _ in range(reps):
                 fn()
         return eager, "eager"
 
