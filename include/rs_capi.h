@@ -528,7 +528,8 @@ int rs_din_attention_ids_cand_fwd(const void* hist, int id_kind,
  * rs_din_attention_ids_cand_fwd, then BatchNormalization (in_scale / in_shift,
  * as rs_mlp_affine_fwd) + the PReLU tower + Dense(1, sigmoid) of
  * rs_mlp_affine_pieces_fwd over the input [pooled (k) | cand rows (k) |
- * pieces] — the pieces must cover columns 2k .. dims[0]-1 (in_cols >= 2k) —
+ * pieces] — the pieces must cover columns 2k .. dims[0]-1 (in_cols >= 2k;
+ * n_pieces = 0 when dims[0] == 2k) —
  * writing y [B] (rows y_stride apart).  Bit-identical to those two launches.
  * pooled (optional, rows pooled_stride apart) also receives the attention
  * output.  rs_din_forward_ids_supported: 1 when the shape takes the fused

@@ -1041,9 +1041,12 @@ extern "C" int rs_din_forward_ids(const void* hist, int id_kind, int64_t hist_st
              "rs_din_forward_ids: shape not supported by the fused launch (rs_din_forward_ids_supported)");
   RS_REQUIRE(dims[n_layers] == 1 && y_stride >= 1, "rs_din_forward_ids: the tower must end in one unit");
   DinTower tw{};
-  int st = concat_fill(n_pieces, widths, in_cols, kinds, srcs, src_strides, tables, vocabs, dims[0],
-                       "rs_din_forward_ids", tw.pc);
-  if (st != RS_OK) return st;
+  RS_REQUIRE(n_pieces >= 0, "rs_din_forward_ids: n_pieces < 0");
+  if (n_pieces > 0) {  // (dims[0] == 2k, which rs_din_forward_ids_supported accepts, has no piece: pc stays empty)
+    const int st = concat_fill(n_pieces, widths, in_cols, kinds, srcs, src_strides, tables, vocabs, dims[0],
+                               "rs_din_forward_ids", tw.pc);
+    if (st != RS_OK) return st;
+  }
   for (int p = 0; p < n_pieces; ++p)
     RS_REQUIRE(in_cols[p] >= 2 * k, "rs_din_forward_ids: piece %d overlaps the pooled / candidate columns", p);
   RS_REQUIRE(tw.pc.ncol == dims[0] - 2 * k, "rs_din_forward_ids: the pieces must cover columns 2k .. %d", dims[0] - 1);

@@ -477,6 +477,10 @@ __device__ __forceinline__ void embed_fm_body(const EmbedFmArgs& a, const MlpArg
     }
   } else {
     late_args();
+    // a wave with no field (F < NW, one slot per wave) may still own a dense
+    // k-step: fetch_ids, which requests the dense block for the others, never
+    // runs for it (without this its dense features entered as zeros)
+    if (!coop && aF > 0 && !has_pass(0)) load_dense();
     for (int cg = 0; has_pass(cg); cg += PS) {
       issue_b(cg, P0);
       issue_rows(cg, P0, false);
