@@ -1195,6 +1195,47 @@ int rs_adam_update_multi(int count, float* const* w, const float* const* grad,
                          float eps, const int64_t* step, rs_stream_t stream);
 int rs_adam_advance(int64_t* step, rs_stream_t stream);
 
+/* ----------------------------------------------- DSSM retrieval (a20)
+ * rs_topn_inner_product: exact top-N by inner product.  user [U, E], item
+ * [I, E] (rows *_stride apart); for every user row u the N items with the
+ * largest score(u, i) = sum_k user[u, k] item[i, k], ordered by the key
+ * (score descending, item position ascending): out_idx [U, N] the positions
+ * into item, out_score [U, N] the scores, both contiguous.  A tie in score
+ * goes to the lower position.  Where I < N the slots past I hold position -1
+ * and score -inf (I = 0: every slot).
+ *
+ * Two kernels (csrc/topn.hip).  The partial kernel runs on a grid of (64-row
+ * user tiles) x (item splits): the user tile in LDS, 8 waves walking the
+ * split's 16-item tiles with v_mfma_f32_16x16x4_f32 (an item tile's operand
+ * loaded once and used by the four 16-row blocks), a sorted best-N list and a
+ * 32-entry candidate queue per row in LDS; a score enters the queue only if
+ * it beats the row's N-th key.  The merge kernel (one workgroup per user)
+ * merges the splits' sorted lists from the workspace pairwise in LDS; with one
+ * split the partial kernel writes the result itself.  A score is one MFMA
+ * chain per pair, the same bits wherever the pair falls, and every comparison
+ * is on the 64-bit key (score, ~position), so the output is bit-identical for
+ * every item_splits.  item_splits 0: chosen from U and I (two workgroups per
+ * CU, at least 64 tiles per split); otherwise clamped to 1..64 and to the
+ * number of 16-item tiles.  No [U, I] buffer, no global atomics; the
+ * workspace (rs_topn_inner_product_workspace_size bytes for the same U, I, N,
+ * item_splits; 0 with one split in effect; 8-byte aligned) need not be
+ * zeroed.  Item rows that are not 16-byte aligned, or E % 4 != 0, are loaded
+ * by scalars.  Inputs are taken as finite: a NaN score gets some rank and
+ * breaks nothing.  rs_topn_inner_product_ok(E, N): 1 for 1 <= E <= 512,
+ * 1 <= N <= 128 and 64 (rup(E, 64) + 8) 4 + 64 (N + 32) 8 + 784 bytes of LDS
+ * within 160 KiB — every (E <= 256, N <= 128); E = 512 up to N = 26.  A
+ * refused shape is RS_ERR_ARG.  I < 2^31.  Stream-ordered, graph-capturable,
+ * no allocation, no host synchronisation; nothing is launched for U = 0.    */
+int rs_topn_inner_product_ok(int E, int N);
+int64_t rs_topn_inner_product_workspace_size(int64_t U, int64_t I, int N,
+                                             int item_splits);
+int rs_topn_inner_product(const float* user, int64_t user_stride, int64_t U,
+                          const float* item, int64_t item_stride, int64_t I,
+                          int E, int N, int item_splits /* 0 = auto */,
+                          int32_t* out_idx /* [U, N] */,
+                          float* out_score /* [U, N] */, void* workspace,
+                          int64_t workspace_bytes, rs_stream_t stream);
+
 /* ------------------------------------------ wide part of Wide&Deep (a17)
  * WideLayer.call (layer/interaction.py:11-26: w0 + x @ w) on the compact form
  * of WideDeep's wide input (model/wideDeep.py:22-34): x = [dense (nd) | dense

@@ -15,6 +15,7 @@ from .layers import (AFMLayer, Attention, AttentionLayer, BatchNormalization, Cr
 from .models import AFM, DCN, DIEN, DIN, DSSM, FFM, FM, MMOE, NFM, PNN, DeepCrossing, DeepFM, WideDeep  # noqa: F401
 from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, get_feature_names  # noqa: F401
 from .negative import NegativeSampler, recall_N, sampledsoftmaxloss  # noqa: F401
+from .retrieval import topn_inner_product, topn_ok  # noqa: F401
 from .dataset import create_criteo_dataset, denseFeature, features_dict, sparseFeature  # noqa: F401
 
 __version__ = "0.1.0"

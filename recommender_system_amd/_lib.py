@@ -123,6 +123,9 @@ SIGNATURES = {
     "rs_embedding_grad_accum": (I, [P, L, I, P, I, L, I, P, I, I, P, L, L, P, P, P]),
     "rs_adam_update_multi": (I, [I, P, P, P, P, P, P, F, F, F, F, P, P]),
     "rs_adam_advance": (I, [P, P]),
+    "rs_topn_inner_product_ok": (I, [I, I]),
+    "rs_topn_inner_product_workspace_size": (L, [L, L, I, I]),
+    "rs_topn_inner_product": (I, [P, L, L, P, L, L, I, I, I, P, P, P, L, P]),
     "rs_gru_prepared_size": (L, [I, I]),
     "rs_gru_prepare": (I, [I, I, P, P, P, P, P]),
     "rs_gru_fwd": (I, [P, L, L, I, I, I, P, P, P, L, L, P]),

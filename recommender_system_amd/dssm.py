@@ -250,6 +250,70 @@ class DSSM(KerasModule):
     def item_embedding(self, inputs, check_ids=True, fused=True):
         return self._embedding(self.item_tower, inputs, fused, check_ids)
 
+    # ---- retrieval
+    def _predict(self, tw, inputs, batch_size, check_ids, fused):
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("DSSM: batch_size must be at least 1")
+        n = len(inputs[(tw.sparse_cols + tw.varlen_cols + tw.dense_cols)[0].name])
+        if n == 0:
+            return torch.empty(0, tw.out_width, dtype=torch.float32, device=self._dev)
+        return torch.cat([self._embedding(tw, {k: v[i:i + batch_size] for k, v in inputs.items()}, fused, check_ids)
+                          for i in range(0, n, batch_size)])
+
+    def predict_user_embedding(self, inputs, batch_size=4096, check_ids=True, fused=True):
+        """The reference's user_embedding_model.predict(inputs, batch_size=2**12)
+        (model/dssm.py:154-160): ``user_embedding`` over sequential batches of
+        ``batch_size`` rows (the last one short), concatenated [rows, E]."""
+        return self._predict(self.user_tower, inputs, batch_size, check_ids, fused)
+
+    def predict_item_embedding(self, inputs, batch_size=4096, check_ids=True, fused=True):
+        """item_embedding_model.predict: ``item_embedding`` over batches, concatenated."""
+        return self._predict(self.item_tower, inputs, batch_size, check_ids, fused)
+
+    def retrieve(self, user_inputs, item_inputs, N=50, batch_size=4096, fused=None, item_ids=None):
+        """(item_ids int64 [U, N], score float32 [U, N]): for every user the N
+        items with the largest u . v, best first (a tie goes to the item that
+        comes first in ``item_inputs``); padded with (-1, -inf) where there are
+        fewer than N items.  ``user_inputs`` / ``item_inputs``: the towers'
+        input dicts (embedded in batches of ``batch_size``), or an embedding
+        matrix computed before (``predict_*_embedding``).  The ids are
+        ``item_ids`` if given, else ``item_inputs[sampler_config.item_name]``,
+        else (no sampler_config, or a precomputed item matrix) the positions.
+        ``fused``: retrieval.topn_inner_product's — None / True the
+        rs_topn_inner_product kernel, False the torch composition."""
+        from .retrieval import topn_inner_product
+        is_matrix = lambda x: not isinstance(x, dict)  # noqa: E731
+        u = _to_device_f32(user_inputs, self._dev) if is_matrix(user_inputs) else \
+            self.predict_user_embedding(user_inputs, batch_size)
+        v = _to_device_f32(item_inputs, self._dev) if is_matrix(item_inputs) else \
+            self.predict_item_embedding(item_inputs, batch_size)
+        if item_ids is None and not is_matrix(item_inputs) and self.sampler_config is not None:
+            item_ids = item_inputs[self.sampler_config.item_name]
+        pos, score = topn_inner_product(u, v, N, fused=fused)
+        pos = pos.to(torch.int64)
+        if item_ids is None:
+            return pos, score
+        ids = torch.as_tensor(item_ids).to(self._dev).reshape(-1).to(torch.int64)
+        if ids.numel() != v.shape[0]:
+            raise ValueError(f"DSSM.retrieve: {ids.numel()} item ids for {v.shape[0]} items")
+        if ids.numel() == 0:
+            return pos, score
+        return torch.where(pos < 0, pos, ids[pos.clamp(min=0)]), score
+
+    def recall(self, user_inputs, true_items, item_inputs, N=50, batch_size=4096, fused=None, item_ids=None):
+        """The mean over the users of ``recall_N([true item], retrieved ids, N)``
+        (utils/negative.py:53-54 with one true item per user): the share of users
+        whose true item is among their N retrieved.  The hit test runs on the
+        device; one number comes back."""
+        ids, _ = self.retrieve(user_inputs, item_inputs, N, batch_size, fused, item_ids)
+        t = torch.as_tensor(true_items).to(self._dev).reshape(-1).to(torch.int64)
+        if t.numel() != ids.shape[0]:
+            raise ValueError(f"DSSM.recall: {t.numel()} true items for {ids.shape[0]} users")
+        if t.numel() == 0:
+            raise ValueError("DSSM.recall: no users")
+        return float((ids == t.unsqueeze(1)).any(1).to(torch.float32).mean())
+
     def _forward(self, inputs, check_ids, fused):
         u = self._embedding(self.user_tower, inputs, fused, check_ids)
         v = self._embedding(self.item_tower, inputs, fused, check_ids)
