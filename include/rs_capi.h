@@ -790,6 +790,90 @@ int rs_mmoe_fwd(const float* x, int64_t x_stride, int d, int hidden,
                 float* y, int64_t y_task_stride, int64_t y_stride,
                 int64_t batch, rs_stream_t stream);
 
+/* Training MMOE (MMOE.train_step).  With L = n_tower_layers >= 1, n_l =
+ * tower_dims[l + 1] (n_{L-1} = Nout), N1 = (H + T) * E:
+ *   z_t = tower_t(mix_t) [B, Nout]                              (rs_mmoe_fwd)
+ *   loss[t, b] = mean_j (max(z, 0) - z y + log1p(exp(-|z|)))   (the sigmoid
+ *     cross-entropy of the towers' logits: BinaryCrossentropy(from_logits=
+ *     True) per output, Keras' sum over the outputs weighted by loss_weights)
+ *   G[b, t * Nout + j] = w_t * (sigmoid(z_t[b, j]) - y_t[b, j]) / (B * Nout)
+ *   delta_{L-1} = G;  delta_{l-1} = (delta_l W_{t,l}^T) [a_{t,l-1} > 0] (no
+ *     mask below a linear hidden layer);  dmix_t = delta_0 W_{t,0}^T
+ *   dp_t[e] = sum_h dmix_t[h] expert[h, e]
+ *   dlogit_t[e] = p_t[e] * (dp_t[e] - sum_e' p_t[e'] dp_t[e'])
+ *   dexp[h, e] = [expert[h, e] > 0] * sum_t p_t[e] dmix_t[h]
+ *   dz1 [B, N1]: column h * E + e = dexp[h, e], column H * E + t * E + e =
+ *     dlogit_t[e] (the forward's stage-1 column order: x^T dz1 read as
+ *     [d, H * E | T * E] is d expert_matrix [d, H, E], then the T gate
+ *     matrices' gradients; its column sums are the bias gradients)
+ *   dx = dz1 W1^T [B, d]
+ * Every sum has one fixed order (h, e', t ascending), there are no atomics, a
+ * row's result does not depend on the batch or on its place in its tile.
+ * Masks are post-activation > 0 (rs_gemm's mask epilogue).  Hidden tower
+ * activations: RS_ACT_RELU or RS_ACT_NONE; the output layer RS_ACT_NONE.
+ * rs_mmoe_train_ok: 1 when the training entries take the shape: rs_mmoe_ok's
+ * conditions, L >= 1, and the backward's three LDS tiles fit: with maxw =
+ * max(roundup(d, 16), roundup(N1, 16), T * roundup(w, 16) over w in {H,
+ * tower widths}), 4 * (48 * (roundup(maxw, 64) + 8) + 4096) <= 160 KiB.  It
+ * never accepts a shape rs_mmoe_ok refuses.
+ * saved (rs_mmoe_saved_size floats, -1 on a refused shape or batch < 0):
+ *   B * (H * E + T * E + T * H + T * sum_{l < L-1} n_l)
+ * = [expert [B, H * E] (column h * E + e, post-relu) | gates [B, T * E] |
+ *    mix [B, T * H] | a_0 .. a_{L-2}, a_l [B, T * n_l] with task t at columns
+ *    t * n_l], dense row-major.
+ * rs_mmoe_train_fwd: rs_mmoe_fwd on the same `prepared` image, y
+ * bit-identical, that also stores `saved`.
+ * rs_mmoe_head_grad: the elementwise head.  z / labels: task t's [B, Nout]
+ * at + t * task_stride, rows stride apart; loss_weights: HOST float[T] or
+ * NULL (all 1); G [B, T * Nout], rows G_stride apart; loss [T, B] or NULL
+ * (unweighted).
+ * The backward image (rs_mmoe_bwd_prepared_size floats, -1 on a refused
+ * shape; Kp_l / Np_l as above):
+ *   sum_l T * Kp_l * Np_l + roundup(N1, 16) * roundup(d, 16)
+ * = [chain layer L-1 .. 0 | W1^T]: chain layer l = the T tasks' W_{t,l}^T
+ * ([Np_l, Kp_l]) in the forward's B-fragment layout one after another, no
+ * biases; W1^T [roundup(N1, 16), roundup(d, 16)] with its rows in the
+ * stage-1 column order.  rs_mmoe_prepare_bwd packs it (pointers as
+ * rs_mmoe_prepare's).
+ * rs_mmoe_bwd: ONE launch over 16-sample tiles for the whole data path.
+ * deltas [B * T * sum_{l < L-1} n_l] has the layout of saved's a_l blocks
+ * (delta_l = dL/d(pre-activation of hidden layer l); may be NULL when L = 1);
+ * dz1 [B, N1], rows dz1_stride apart; dx [B, d], rows dx_stride apart, or
+ * NULL = not computed (dz1 and deltas are bit-identical either way).  dmix,
+ * dp and every other intermediate stay in LDS.
+ * Stream-ordered, graph-capturable; arguments are validated before any device
+ * work; nothing is launched for batch 0.                                     */
+int rs_mmoe_train_ok(int d, int hidden, int n_experts, int n_tasks,
+                     int n_tower_layers, const int* tower_dims);
+int64_t rs_mmoe_saved_size(int d, int hidden, int n_experts, int n_tasks,
+                           int n_tower_layers, const int* tower_dims,
+                           int64_t batch);
+int rs_mmoe_train_fwd(const float* x, int64_t x_stride, int d, int hidden,
+                      int n_experts, int n_tasks, int n_tower_layers,
+                      const int* tower_dims, const int* tower_acts,
+                      const float* prepared, float* saved, float* y,
+                      int64_t y_task_stride, int64_t y_stride, int64_t batch,
+                      rs_stream_t stream);
+int rs_mmoe_head_grad(const float* z, int64_t z_task_stride, int64_t z_stride,
+                      const float* labels, int64_t labels_task_stride,
+                      int64_t labels_stride, const float* loss_weights,
+                      int n_out, int n_tasks, int64_t batch, float* G,
+                      int64_t G_stride, float* loss, rs_stream_t stream);
+int64_t rs_mmoe_bwd_prepared_size(int d, int hidden, int n_experts,
+                                  int n_tasks, int n_tower_layers,
+                                  const int* tower_dims);
+int rs_mmoe_prepare_bwd(int d, int hidden, int n_experts, int n_tasks,
+                        const float* expert_matrix,
+                        const float* const* gate_matrix, int n_tower_layers,
+                        const int* tower_dims, const float* const* tower_W,
+                        float* prepared_bwd, rs_stream_t stream);
+int rs_mmoe_bwd(const float* saved, const float* G, int64_t G_stride, int d,
+                int hidden, int n_experts, int n_tasks, int n_tower_layers,
+                const int* tower_dims, const int* tower_acts,
+                const float* prepared_bwd, float* deltas, float* dz1,
+                int64_t dz1_stride, float* dx, int64_t dx_stride,
+                int64_t batch, rs_stream_t stream);
+
 /* ------------------------------- DIEN interest evolution (a19), forward
  * model/dien.py:54-70 on a behaviour sequence keys [B, T, D], a candidate q
  * [B, D] and lengths len [B] (int32 or int64; position t is valid iff t <

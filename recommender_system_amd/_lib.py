@@ -103,6 +103,13 @@ SIGNATURES = {
     "rs_mmoe_prepared_size": (L, [I, I, I, I, I, P]),
     "rs_mmoe_prepare": (I, [I, I, I, I, P, P, P, P, I, P, P, P, P, P]),
     "rs_mmoe_fwd": (I, [P, L, I, I, I, I, I, P, P, P, P, L, P, L, L, L, P]),
+    "rs_mmoe_train_ok": (I, [I, I, I, I, I, P]),
+    "rs_mmoe_saved_size": (L, [I, I, I, I, I, P, L]),
+    "rs_mmoe_train_fwd": (I, [P, L, I, I, I, I, I, P, P, P, P, P, L, L, L, P]),
+    "rs_mmoe_head_grad": (I, [P, L, L, P, L, L, P, I, I, L, P, L, P, P]),
+    "rs_mmoe_bwd_prepared_size": (L, [I, I, I, I, I, P]),
+    "rs_mmoe_prepare_bwd": (I, [I, I, I, I, P, P, I, P, P, P, P]),
+    "rs_mmoe_bwd": (I, [P, P, L, I, I, I, I, I, P, P, P, P, P, L, P, L, L, P]),
     "rs_dien_evolution_ok": (I, [I, I, I, P, I]),
     "rs_dien_prepared_size": (L, [I, I, P]),
     "rs_dien_prepare": (I, [I, P, P, P, P, P, I, P, I, P, P, P, P, P, P, P, P, P]),

@@ -440,6 +440,61 @@ def augru_backward(augru, x, scores, lengths, weight_norm, saved, dlast, st, wan
     return dx, ds, da, dW, dU
 
 
+# ----------------------------------------------------- MMOE's step (mmoe_train.hip)
+MMOE_L2 = 1e-4  # l2(1e-4) on every mmoe_layer weight (layer/interaction.py:441-477); the towers declare none
+
+
+def mmoe_labels(labels, T, B, nout, device):
+    """The labels [T, B, Nout] (float32, contiguous) from a list of T arrays
+    [B] / [B, Nout] or one [T, B(, Nout)] tensor."""
+    if isinstance(labels, (list, tuple)):
+        if len(labels) != T:
+            raise ValueError(f"MMOE: {T} tasks, got {len(labels)} label arrays")
+        y = torch.stack([_layers._to_device_f32(l, device).reshape(B, nout) for l in labels])
+    else:
+        y = _layers._to_device_f32(labels, device).reshape(T, B, nout)
+    return y.contiguous()
+
+
+def mmoe_head(z, y, loss_weights, st):
+    """rs_mmoe_head_grad on the towers' logits z [T, B, Nout] and labels y of
+    the same shape: (G [B, T Nout] = dL/dz with the weights and the two means
+    applied, the unweighted per-sample losses [T, B])."""
+    T, B, nout = z.shape
+    if loss_weights is not None and len(loss_weights) != T:
+        raise ValueError(f"MMOE: {T} tasks, got {len(loss_weights)} loss_weights")
+    lw = None if loss_weights is None else (_lib.C.c_float * T)(*[float(w) for w in loss_weights])
+    G = torch.empty(B, T * nout, dtype=torch.float32, device=z.device)
+    loss = torch.empty(T, B, dtype=torch.float32, device=z.device)
+    call("rs_mmoe_head_grad", ptr(z), z.stride(0), z.stride(1), ptr(y), y.stride(0), y.stride(1), lw, nout, T, B,
+         ptr(G), G.stride(0), ptr(loss), st)
+    return G, loss
+
+
+def mmoe_layer_grads(layer, x, dz1, gw, emp, st, d_in=False):
+    """The mmoe_layer's weight gradients from dz1 [B, (H + T) E] (the
+    forward's stage-1 column order): one x^T dz1 contraction and column sum
+    for the experts and one per gate (dense_backward on column views), each
+    into a contiguous buffer of the parameter's own shape.  Returns ({name:
+    grad}, dL/dx or None — the T + 1 blocks' dz W^T summed in block order)."""
+    d, H, E, T = layer.input_dim, layer.hidden_units, layer.num_experts, layer.num_tasks
+    HE = H * E
+    out, dx = {}, None
+    dW, db, below = dense_backward(layer.expert_matrix.view(d, HE), x, dz1[:, :HE], gw, emp, st, d_in=d_in)
+    out["expert_matrix"] = dW.view(d, H, E)
+    if layer.use_expert_bias:
+        out["expert_bias"] = db.view(H, E)
+    dx = below
+    for t, gm in enumerate(layer.gate_matrix):
+        dW, db, below = dense_backward(gm, x, dz1[:, HE + t * E:HE + (t + 1) * E], gw, emp, st, d_in=d_in)
+        out[f"gate_matrix{t}"] = dW
+        if layer.use_gate_bias:
+            out[f"gate_bias{t}"] = db
+        if d_in:
+            dx = dx + below
+    return out, dx
+
+
 # ------------------------------------------------ FM part of a DeepFM step
 def fm_xv(x, v, gw, st, out=None):
     """s = x v [B, kfm] (rs_gemm), what rs_fm_x_grad / rs_fm_param_grads read."""

@@ -62,7 +62,8 @@ from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, build_input
 from ._train_ops import (_Dropout, _check_train_tower, _dnn_apply, _dnn_backward, _dnn_train_forward,  # noqa: F401
                          _dnn_updates, _dropout_rate, _dropout_rng, _split_criteo, _subseed, bce_head,
                          bce_head_logit, bn_train_bwd, bn_train_fwd, dense_backward, embedding_sgd,
-                         embedding_sgd_strided, fm_backward, fm_xv, gemm_need, gemm_ws, scratch)
+                         embedding_sgd_strided, fm_backward, fm_xv, gemm_need, gemm_ws, scratch,
+                         MMOE_L2, mmoe_head, mmoe_labels, mmoe_layer_grads)
 
 
 class FM(KerasModule):
@@ -1679,7 +1680,8 @@ class MMOE(KerasModule):
     output_dim, activation='relu', use_expert_bias=True, use_gate_bias=True) —
     model/mmoe.py:10-32: a float matrix x [B, d] through mmoe_layer, then task
     t's tower_layer on task t's mix; returns num_tasks tensors [B, output_dim].
-    Forward only, as the reference (it has no loss or fit loop for MMOE).
+    ``train_step`` / ``fit`` train it on Keras' multi-output loss (see
+    ``gradients``); the reference itself has no fit loop for MMOE.
 
     The mmoe_layer builds from the input width on the first call (or
     ``input_dim``); the towers are built at construction (their input is
@@ -1724,9 +1726,195 @@ class MMOE(KerasModule):
 
     def _invalidate(self):
         self.__dict__.pop("_mmoe_prep", None)
+        self.__dict__.pop("_mmoe_prep_bwd", None)
 
     def _dims(self):
         return _mmoe_dims(self.mmoe_layer.hidden_units, list(self.tower_layer))
+
+    def train_fused_ok(self):
+        """Whether the training kernels (rs_mmoe_train_fwd / rs_mmoe_bwd) take
+        this model: 'relu' or linear towers and a shape rs_mmoe_train_ok accepts."""
+        m = self.mmoe_layer
+        dims = self._dims()
+        return bool(m.built and self.activation in ("relu", "linear", None) and len(dims) - 1 <= _MMOE_MAXL
+                    and _lib.lib().rs_mmoe_train_ok(m.input_dim, m.hidden_units, m.num_experts, m.num_tasks,
+                                                    len(dims) - 1, (C.c_int * len(dims))(*dims)))
+
+    def prepared_bwd(self):
+        """The backward weight image (rs_mmoe_prepare_bwd: every tower layer's
+        kernels transposed, top layer first, and W1^T), cached under the key
+        of ``prepared``."""
+        towers = list(self.tower_layer)
+        key = tuple((p._version, p.data_ptr()) for p in _mmoe_params(self.mmoe_layer, towers))
+        ent = self.__dict__.get("_mmoe_prep_bwd")
+        if ent is None or ent[0] != key:
+            m = self.mmoe_layer
+            dims = self._dims()
+            n = len(dims) - 1
+            ci = (C.c_int * len(dims))(*dims)
+            size = _lib.lib().rs_mmoe_bwd_prepared_size(m.input_dim, m.hidden_units, m.num_experts, m.num_tasks, n, ci)
+            if size < 0:
+                _lib.check(-1, "rs_mmoe_bwd_prepared_size")
+            pa = lambda ts: (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
+            img = torch.empty(size, dtype=torch.float32, device=self._dev)
+            call("rs_mmoe_prepare_bwd", m.input_dim, m.hidden_units, m.num_experts, m.num_tasks, ptr(m.expert_matrix),
+                 pa(m.gate_matrix), n, ci, pa([l.kernel for tw in towers for l in tw._layers()]), ptr(img),
+                 _lib.stream())
+            ent = self.__dict__["_mmoe_prep_bwd"] = (key, img)
+        return ent[1]
+
+    def gradients(self, x, labels, loss_weights=None, fused=None, want_dx=False):
+        """The gradients of one training step's loss without its l2 terms:
+        ({Keras weight name: gradient, of the weight's shape}, the per-sample
+        losses [T, B] (unweighted, before any step), dL/dx [B, d] or None).
+
+        The loss is Keras' for a model with T outputs compiled as compile_fit
+        does (utils/compile_fit.py:9-15): the per-output losses summed with
+        ``loss_weights`` (default 1) — each the mean over the batch and over
+        output_dim of the sigmoid cross-entropy of the tower's logits
+        (BinaryCrossentropy(from_logits=True): tower_layer ends in a linear
+        Dense, on which the probability form has zero gradient outside (0, 1);
+        DESIGN.md "Out of scope") — plus mmoe_layer's l2(1e-4) terms, which
+        ``train_step`` applies in the update.
+
+        ``fused=True``: rs_mmoe_train_fwd (the forward's launch, which also
+        stores the experts, gates, mixes and hidden activations),
+        rs_mmoe_head_grad, and the whole backward data path in one launch
+        (rs_mmoe_bwd: every tower delta, dz1 = [dexpert | dgate logits] and,
+        with ``want_dx``, dL/dx).  ``fused=False``: rs_dense_fwd for the
+        experts and per gate, torch elementwise ops for the softmax, the mix
+        and their backward, _dnn_train_forward / _dnn_backward per tower.  Both
+        take the weight gradients from the same deterministic blocks
+        (rs_gemm(trans_a) + rs_col_sum per tensor).  ``None`` picks fused when
+        ``train_fused_ok()``; ``True`` raises where the kernels refuse."""
+        if self._dev.type != "cuda":
+            raise NotImplementedError("MMOE.train_step: training runs only on a HIP device")
+        for tw in self.tower_layer:
+            _check_train_tower("MMOE", tw)
+        m = self.mmoe_layer
+        x = _mmoe_input(x, m)
+        if fused is None:
+            fused = self.train_fused_ok()
+        elif fused and not self.train_fused_ok():
+            raise ValueError("MMOE.train_step(fused=True): the MMOE training kernels do not take this shape")
+        towers = [tw._layers() for tw in self.tower_layer]
+        (B, d), H, E, T = x.shape, m.hidden_units, m.num_experts, m.num_tasks
+        if B == 0:
+            raise ValueError("MMOE.train_step: an empty batch")
+        dims = self._dims()
+        n, nout, HE, st, dev = len(dims) - 1, self.output_dim, H * E, _lib.stream(), self._dev
+        emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        y = mmoe_labels(labels, T, B, nout, dev)
+        z = emp(T, B, nout)
+        gw = gemm_ws(self, gemm_need([(d, HE, B), (d, E, B)] + [(*L.kernel.shape, B) for L in towers[0]]))
+        grads = {}
+        if fused:
+            ci = (C.c_int * (n + 1))(*dims)
+            ca = (C.c_int * n)(*([_lib.ACT[self.activation]] * (n - 1) + [0]))
+            size = _lib.lib().rs_mmoe_saved_size(d, H, E, T, n, ci, B)
+            if size < 0:
+                _lib.check(-1, "rs_mmoe_saved_size")
+            saved = emp(size)
+            call("rs_mmoe_train_fwd", ptr(x), x.stride(0), d, H, E, T, n, ci, ca, ptr(self.prepared()), ptr(saved),
+                 ptr(z), z.stride(0), z.stride(1), B, st)
+            G, loss = mmoe_head(z, y, loss_weights, st)
+            hid = dims[1:-1]
+            deltas = emp(max(B * T * sum(hid), 1))
+            dz1 = emp(B, (H + T) * E)
+            dx = emp(B, d) if want_dx else None
+            call("rs_mmoe_bwd", ptr(saved), ptr(G), G.stride(0), d, H, E, T, n, ci, ca, ptr(self.prepared_bwd()),
+                 ptr(deltas), ptr(dz1), dz1.stride(0), ptr(dx), d, B, st)
+            # views of saved / deltas: layer l's input and delta, all tasks side by side
+            so = B * (HE + T * E)
+            ins, dels, do = [saved[so:so + B * T * H].view(B, T * H)], [], 0
+            so += B * T * H
+            for w in hid:
+                ins.append(saved[so:so + B * T * w].view(B, T * w))
+                dels.append(deltas[do:do + B * T * w].view(B, T * w))
+                so, do = so + B * T * w, do + B * T * w
+            dels.append(G)
+            for t, layers in enumerate(towers):
+                for l, L in enumerate(layers):
+                    K, N = L.kernel.shape
+                    dW, db, _ = dense_backward(L.kernel, ins[l][:, t * K:(t + 1) * K], dels[l][:, t * N:(t + 1) * N], gw,
+                                               emp, st, d_in=False)
+                    grads[(t, l)] = (dW, db)
+            lg, _ = mmoe_layer_grads(m, x, dz1, gw, emp, st)
+        else:
+            expert = emp(B, HE)
+            call("rs_dense_fwd", ptr(x), x.stride(0), ptr(m.expert_matrix), ptr(m.expert_bias), None, _lib.ACT["relu"],
+                 ptr(expert), HE, B, d, HE, st)
+            exp3 = expert.view(B, H, E)
+            gb, ps, tacts = m.gate_bias, [], []
+            for t, gm in enumerate(m.gate_matrix):
+                logits = emp(B, E)
+                call("rs_dense_fwd", ptr(x), x.stride(0), ptr(gm), ptr(gb[t]) if gb else None, None, 0, ptr(logits), E,
+                     B, d, E, st)
+                ps.append(torch.softmax(logits, dim=-1))
+                mix = (exp3 * ps[t].unsqueeze(1)).sum(-1)
+                acts, _ = _dnn_train_forward(self, self.tower_layer[t], mix, 0.0, st)
+                self.tower_layer[t].output_layer(acts[-1], out=z[t])
+                tacts.append(acts)
+            G, loss = mmoe_head(z, y, loss_weights, st)
+            dmix = []
+            for t, layers in enumerate(towers):
+                tg, below = _dnn_backward(layers, tacts[t], G[:, t * nout:(t + 1) * nout], gw, emp, st)
+                for l, (_, dW, db) in enumerate(reversed(tg)):
+                    grads[(t, l)] = (dW, db)
+                dmix.append(below)
+            dexp = torch.zeros_like(exp3)
+            dlog = []
+            for t in range(T):
+                dexp = dexp + dmix[t].unsqueeze(2) * ps[t].unsqueeze(1)
+                dp = (dmix[t].unsqueeze(2) * exp3).sum(1)
+                dlog.append(ps[t] * (dp - (ps[t] * dp).sum(-1, keepdim=True)))
+            dz1 = torch.cat([(dexp * (exp3 > 0)).reshape(B, HE)] + dlog, 1)
+            lg, dx = mmoe_layer_grads(m, x, dz1, gw, emp, st, d_in=want_dx)
+        out = {"mmoe_layer/" + k: v for k, v in lg.items()}
+        for t, tw in enumerate(self.tower_layer):
+            for l in range(n):
+                name = f"tower_layer_{t}/" + (f"dense_{l}" if l < n - 1 else "dense_out")
+                out[name + "/kernel"], out[name + "/bias"] = grads[(t, l)]
+        return out, loss, dx
+
+    def train_step(self, x, labels, lr=0.01, loss_weights=None, return_loss=False, fused=None, return_dx=False):
+        """One SGD step on the multi-task loss of ``gradients`` (compile_fit's
+        SGD(lr) on Keras' summed per-output losses plus the layers'
+        regularisation losses): w -= lr (grad + 2 l2 w) in one
+        rs_sgd_update_multi launch, l2 = 1e-4 on the mmoe_layer tensors that
+        exist under the ``use_*_bias`` flags and 0 on the towers; every weight
+        is updated in place.  ``labels``: a list of T arrays [B] / [B,
+        output_dim] or one [T, B(, output_dim)] tensor.  Returns the
+        per-sample losses [T, B] before the step if ``return_loss``, dL/dx
+        [B, d] if ``return_dx``, the pair if both."""
+        grads, loss, dx = self.gradients(x, labels, loss_weights, fused, return_dx)
+        ups = [(p, grads[name], p.numel(), MMOE_L2 if name.startswith("mmoe_layer/") else 0.0)
+               for name, p in self.keras_weights().items()]
+        _lib.sgd_update_multi(ups, lr, _lib.stream())
+        self._weights_changed()
+        ret = tuple(v for v, want in ((loss, return_loss), (dx, return_dx)) if want)
+        return None if not ret else ret[0] if len(ret) == 1 else ret
+
+    def fit(self, x, labels, batch_size=32, epochs=10, lr=0.01, loss_weights=None):
+        """compile_fit's loop (utils/compile_fit.py:14: model.fit on
+        sequential batches, no shuffle) of ``train_step``.  Returns the
+        history: per epoch, the mean over the samples of the tasks' losses
+        summed with ``loss_weights`` (each batch's losses taken before its
+        step; the l2 terms are not part of it)."""
+        m = self.mmoe_layer
+        x = _mmoe_input(x, m)
+        B, T = x.shape[0], m.num_tasks
+        y = mmoe_labels(labels, T, B, self.output_dim, self._dev)
+        w = torch.ones(T, device=self._dev) if loss_weights is None else _to_device_f32(list(loss_weights), self._dev)
+        history = []
+        for _ in range(int(epochs)):
+            total = torch.zeros((), dtype=torch.float64, device=self._dev)
+            for b0 in range(0, B, int(batch_size)):
+                b1 = min(b0 + int(batch_size), B)
+                loss = self.train_step(x[b0:b1], y[:, b0:b1], lr, loss_weights, return_loss=True)
+                total += (loss.double() * w.double().unsqueeze(1)).sum()
+            history.append(float(total) / max(B, 1))
+        return history
 
     def fused_ok(self):
         m = self.mmoe_layer
