@@ -317,6 +317,27 @@ def ptr(t) -> int | None:
     return t.data_ptr()
 
 
+def ptrs(ts):
+    """c_void_p array of the tensors' device pointers (None -> null).  Never
+    zero-length, so an empty list still passes a valid pointer."""
+    return (C.c_void_p * max(len(ts), 1))(*[ptr(t) for t in ts])
+
+
+def ints(vs):
+    """c_int array of vs (never zero-length, as ``ptrs``)."""
+    return (C.c_int * max(len(vs), 1))(*vs)
+
+
+def sized(name: str, *args, device):
+    """An uninitialised float32 tensor on `device` of the element count the
+    ``*_size`` entry `name` answers for args; a negative answer raises through
+    ``check``."""
+    n = getattr(lib(), name)(*args)
+    if n < 0:
+        check(-1, name)
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
 def sgd_update_multi(updates, lr, st) -> None:
     """One rs_sgd_update_multi launch for [(w, grad, n, l2)] (w / grad device
     tensors or raw pointers; n elements; l2 the Keras l2 factor)."""

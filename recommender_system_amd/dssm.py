@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from . import _lib, _train_ops
-from ._lib import call, ptr
+from ._lib import call, ints, ptr, ptrs
 from ._train_ops import _dropout_rng, _subseed, bce_head_logit, bn_train_bwd, bn_train_fwd, gemm_ws, scratch
 from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, build_input_features
 from .layers import (DNN, InBatchSoftmaxLayer, KerasModule, TowerMixin, _ErrFlag, _ids_tensor, _lengths,
@@ -66,8 +66,7 @@ class _Tower(TowerMixin, KerasModule):
             return False
         dims = [self.input_width] + self.dnn.hidden_units
         n = len(self.dnn.layers)
-        return bool(_lib.lib().rs_dssm_tower_ok(n_pc + n_seq, n, (C.c_int * (n + 1))(*dims),
-                                                (C.c_int * max(n, 1))(*self._acts())))
+        return bool(_lib.lib().rs_dssm_tower_ok(n_pc + n_seq, n, ints(dims), ints(self._acts())))
 
 
 class DSSM(KerasModule):
@@ -206,11 +205,9 @@ class DSSM(KerasModule):
     @staticmethod
     def _piece_arrays(ch):
         n = len(ch)
-        return (n, (C.c_int * n)(*[p[0] for p in ch]), (C.c_int * n)(*[p[1] for p in ch]),
-                (C.c_int * n)(*[-1 if p[3] is None else _lib.id_kind(p[2]) for p in ch]),
-                (C.c_void_p * n)(*[ptr(p[2]) for p in ch]),
-                (C.c_int64 * n)(*[p[2].stride(0) if p[3] is None else 1 for p in ch]),
-                (C.c_void_p * n)(*[ptr(p[3]) for p in ch]),
+        return (n, ints([p[0] for p in ch]), ints([p[1] for p in ch]),
+                ints([-1 if p[3] is None else _lib.id_kind(p[2]) for p in ch]), ptrs([p[2] for p in ch]),
+                (C.c_int64 * n)(*[p[2].stride(0) if p[3] is None else 1 for p in ch]), ptrs([p[3] for p in ch]),
                 (C.c_int64 * n)(*[0 if p[3] is None else p[3].shape[0] for p in ch]))
 
     def _tower_input(self, tw, pieces, seqs, B, err):
@@ -233,7 +230,7 @@ class DSSM(KerasModule):
                 none = (None,) * 7
                 pa = self._piece_arrays(pieces) if pieces else (0,) + none
                 sa = (len(seqs),) + (seq_pool_arrays(seqs) if seqs else (None,) * 12)
-                call("rs_dssm_tower_fwd", *pa, *sa, n, (C.c_int * (n + 1))(*dims), (C.c_int * max(n, 1))(*tw._acts()),
+                call("rs_dssm_tower_fwd", *pa, *sa, n, ints(dims), ints(tw._acts()),
                      ptr(tw.prepared()) if n else None, ptr(out), out.stride(0), B, ptr(err.t), _lib.stream())
         else:
             x = self._tower_input(tw, pieces, seqs, B, err)

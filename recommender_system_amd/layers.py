@@ -56,7 +56,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import call, ptr
+from ._lib import call, ints, ptr, ptrs, sized
 from . import _train_ops
 from ._train_ops import _subseed, scratch
 
@@ -147,8 +147,25 @@ class KerasModule(nn.Module):
                 m._invalidate()
         self._invalidate()
 
+    def _packed(self, slot, params, build, extra=()):
+        """The one cache of everything packed from weights (MFMA operand
+        images, backward images, folded affines): ``build()``'s value for
+        `slot`, rebuilt when a parameter's version or storage, or `extra`,
+        differs from the last build.  One entry per slot; the entry holds the
+        value, so whatever ``build`` returns beside the image (operands a
+        stream still reads) lives as long as the image does.  The training
+        steps move weights through raw pointers, which bumps no version: they
+        end in ``_weights_changed()``.  The dict lives in ``__dict__`` only —
+        not a Module attribute, not in ``state_dict``."""
+        key = (extra, tuple((p._version, p.data_ptr()) for p in params))
+        cache = self.__dict__.setdefault("_packed_cache", {})
+        ent = cache.get(slot)
+        if ent is None or ent[0] != key:
+            ent = cache[slot] = (key, build())
+        return ent[1]
+
     def _invalidate(self):
-        pass
+        self.__dict__.pop("_packed_cache", None)
 
 
 # --------------------------------------------------------------- embedding
@@ -244,8 +261,6 @@ class FMLayer(KerasModule):
         self.k = int(k)
         self.reg_w, self.reg_b = reg_w, reg_b
         self.w0 = self.w1 = self.v = None
-        self._prep = None
-        self._prep_key = None
         if input_dim is not None:
             self.build(input_dim)
 
@@ -259,21 +274,17 @@ class FMLayer(KerasModule):
     def built(self):
         return self.v is not None
 
-    def _invalidate(self):
-        self._prep = None
-        self._prep_key = None
-
     def prepared(self, nd, n_fields, emb_k):
-        """Packed MFMA operand image of (w1, v) for a given x layout."""
-        key = (nd, n_fields, emb_k, self.w1._version, self.v._version, self.w1.data_ptr(), self.v.data_ptr())
-        if self._prep is None or self._prep_key != key:
+        """Packed MFMA operand image of (w1, v) for a given x layout (one
+        image: another layout repacks)."""
+        def build():
             n = _lib.lib().rs_fm_prepared_size(nd, n_fields, emb_k, self.k)
             if n <= 0:
                 raise ValueError("FMLayer: unsupported shape")
-            self._prep = torch.empty(n, dtype=torch.float32, device=self._dev)
-            call("rs_fm_prepare", ptr(self.w1), ptr(self.v), nd, n_fields, emb_k, self.k, ptr(self._prep), _stream())
-            self._prep_key = key
-        return self._prep
+            prep = torch.empty(n, dtype=torch.float32, device=self._dev)
+            call("rs_fm_prepare", ptr(self.w1), ptr(self.v), nd, n_fields, emb_k, self.k, ptr(prep), _stream())
+            return prep
+        return self._packed("fm", (self.w1, self.v), build, extra=(nd, n_fields, emb_k))
 
     def forward(self, inputs):
         x = _to_device_f32(inputs, self._dev)
@@ -299,8 +310,6 @@ class CrossLayer(KerasModule):
         self.reg_w, self.reg_b = reg_w, reg_b
         self.cross_weight = nn.ParameterList()
         self.cross_bias = nn.ParameterList()
-        self._prep = None
-        self._prep_key = None
         if input_dim is not None:
             self.build(input_dim)
 
@@ -327,25 +336,18 @@ class CrossLayer(KerasModule):
                 self.cross_bias[i].copy_(torch.as_tensor(weights[f"b{i}"], dtype=torch.float32).reshape(-1, 1))
         self._invalidate()
 
-    def _invalidate(self):
-        self._prep = None
-        self._prep_key = None
-
     def prepared(self, d):
-        key = tuple((p._version, p.data_ptr()) for p in list(self.cross_weight) + list(self.cross_bias))
-        if self._prep is None or self._prep_key != key:
+        def build():
             L = self.layer_num
-            n = _lib.lib().rs_cross_prepared_size(d, L)
-            self._prep = torch.empty(n, dtype=torch.float32, device=self._dev)
+            prep = sized("rs_cross_prepared_size", d, L, device=self._dev)
             if L:
                 W = torch.stack([w.reshape(-1) for w in self.cross_weight]).contiguous()
                 Bb = torch.stack([b.reshape(-1) for b in self.cross_bias]).contiguous()
             else:
                 W = Bb = None
-            call("rs_cross_prepare", ptr(W), ptr(Bb), d, L, ptr(self._prep), _stream())
-            self._keep = (W, Bb)  # stream-ordered lifetime
-            self._prep_key = key
-        return self._prep
+            call("rs_cross_prepare", ptr(W), ptr(Bb), d, L, ptr(prep), _stream())
+            return prep, (W, Bb)  # the stacked operands: stream-ordered lifetime
+        return self._packed("cross", list(self.cross_weight) + list(self.cross_bias), build)[0]
 
     def forward(self, inputs, out=None):
         x = _to_device_f32(inputs, self._dev)
@@ -400,20 +402,13 @@ class OuterProductLayer(KerasModule):
         with torch.no_grad():
             self.W.copy_(torch.as_tensor(weights["W"], dtype=torch.float32).reshape(self.W.shape))
 
-    def _invalidate(self):
-        self._prep_key = None  # W moved through a raw pointer (training): repack
-
     def prepared(self):
         """W packed into per-lane MFMA fragments (rs_outer_prepare), cached."""
-        key = (self.W._version, self.W.data_ptr())
-        if getattr(self, "_prep_key", None) != key:
-            n = _lib.lib().rs_outer_prepared_size(self.field_num, self.k)
-            if n < 0:
-                _lib.check(-1, "rs_outer_prepared_size")
-            self._prep = torch.empty(n, dtype=torch.float32, device=self._dev)
-            call("rs_outer_prepare", ptr(self.W), self.field_num, self.k, ptr(self._prep), _stream())
-            self._prep_key = key
-        return self._prep
+        def build():
+            prep = sized("rs_outer_prepared_size", self.field_num, self.k, device=self._dev)
+            call("rs_outer_prepare", ptr(self.W), self.field_num, self.k, ptr(prep), _stream())
+            return prep
+        return self._packed("outer", (self.W,), build)
 
     def forward(self, inputs, out=None):
         e = _to_device_f32(inputs, self._dev)
@@ -468,8 +463,7 @@ class FGCNNLayer(KerasModule):
         return self.field_num is not None
 
     def _cfg(self):
-        arr = lambda v: (C.c_int * len(v))(*v)
-        return len(self.filters), arr(self.filters), arr(self.kernel_width), arr(self.pooling_width)
+        return len(self.filters), ints(self.filters), ints(self.kernel_width), ints(self.pooling_width)
 
     def build(self, F, k):
         F, k = int(F), int(k)
@@ -511,9 +505,7 @@ class FGCNNLayer(KerasModule):
                     p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
 
     def _weight_ptrs(self):
-        n = len(self.filters)
-        return ((C.c_void_p * n)(*[ptr(w) for w in self.conv_kernels]),
-                (C.c_void_p * n)(*[ptr(b) for b in self.conv_biases]))
+        return ptrs(self.conv_kernels), ptrs(self.conv_biases)
 
     def _check_shape(self, F, k):
         if not self.built:
@@ -631,18 +623,13 @@ class TowerMixin:
     activations stay in LDS, weights are packed once.  The host class
     provides ``_layers()`` (the Dense layers in order) and ``_dev``."""
 
-    def _invalidate(self):
-        # packed images keyed on tensor versions miss in-place kernel updates
-        # (training steps): drop them
-        self.__dict__.pop("_tower_prep", None)
-
     def tower_ok(self):
         ls = self._layers()
         if not (ls[0].kernel is not None and len(ls) <= _MLP_MAXL and all(l.activation != "dice" for l in ls)
                 and all(d <= _MLP_MAXD for d in self._dims())):
             return False
         dims = self._dims()
-        return _lib.lib().rs_mlp_prepared_size(len(ls), (C.c_int * len(dims))(*dims)) >= 0  # LDS budget
+        return _lib.lib().rs_mlp_prepared_size(len(ls), ints(dims)) >= 0  # LDS budget
 
     def _dims(self):
         ls = self._layers()
@@ -651,26 +638,17 @@ class TowerMixin:
     def prepared(self, in_rows=None):
         """Weights packed in MFMA B-fragment order (rs_mlp_prepare), cached
         until any weight changes (in-place updates bump tensor versions)."""
-        params = [p for l in self._layers() for p in (l.kernel, l.bias, l.alpha) if p is not None]
-        key = (tuple((p._version, p.data_ptr()) for p in params),
-               None if in_rows is None else in_rows._version)
-        cache = self.__dict__.setdefault("_tower_prep", {})
-        slot = None if in_rows is None else in_rows.data_ptr()
-        ent = cache.get(slot)
-        if ent is None or ent[0] != key:
-            ls = self._layers()
-            dims = self._dims()
-            n = len(ls)
-            ci = (C.c_int * (n + 1))(*dims)
-            pa = lambda ts: (C.c_void_p * n)(*[ptr(t) for t in ts])
-            size = _lib.lib().rs_mlp_prepared_size(n, ci)
-            if size < 0:
-                _lib.check(-1, "rs_mlp_prepared_size")
-            prep = torch.empty(size, dtype=torch.float32, device=self._dev)
-            call("rs_mlp_prepare", n, ci, pa([l.kernel for l in ls]), pa([l.bias for l in ls]),
-                 pa([l.alpha for l in ls]), ptr(in_rows), ptr(prep), _stream())
-            ent = cache[slot] = (key, prep, in_rows)  # in_rows kept alive with its packing
-        return ent[1]
+        ls = self._layers()
+        params = [p for l in ls for p in (l.kernel, l.bias, l.alpha) if p is not None]
+
+        def build():
+            n, ci = len(ls), ints(self._dims())
+            prep = sized("rs_mlp_prepared_size", n, ci, device=self._dev)
+            call("rs_mlp_prepare", n, ci, ptrs([l.kernel for l in ls]), ptrs([l.bias for l in ls]),
+                 ptrs([l.alpha for l in ls]), ptr(in_rows), ptr(prep), _stream())
+            return prep, in_rows  # in_rows kept alive with its packing
+        slot, extra = (None, ()) if in_rows is None else (in_rows.data_ptr(), (in_rows._version,))
+        return self._packed(("tower", slot), params, build, extra)[0]
 
     def tower(self, x, extra=None, c0=1.0, c1=1.0, head=False, out=None, in_affine=None):
         """rs_mlp_fwd on x:[M, K] (device, row stride x.stride(0)).  head=True:
@@ -688,11 +666,11 @@ class TowerMixin:
             sc, sh = in_affine
             if sc.numel() != dims[0] or sh.numel() != dims[0]:
                 raise ValueError(f"tower: in_affine needs {dims[0]} scales and shifts")
-            call("rs_mlp_affine_fwd", ptr(x), x.stride(0), ptr(sc), ptr(sh), n, (C.c_int * (n + 1))(*dims),
-                 (C.c_int * n)(*acts), ptr(self.prepared()), ptr(out), out.stride(0), 1 if head else 0, ptr(extra),
+            call("rs_mlp_affine_fwd", ptr(x), x.stride(0), ptr(sc), ptr(sh), n, ints(dims),
+                 ints(acts), ptr(self.prepared()), ptr(out), out.stride(0), 1 if head else 0, ptr(extra),
                  float(c0), float(c1), M, _stream())
             return out
-        call("rs_mlp_fwd", ptr(x), x.stride(0), n, (C.c_int * (n + 1))(*dims), (C.c_int * n)(*acts),
+        call("rs_mlp_fwd", ptr(x), x.stride(0), n, ints(dims), ints(acts),
              ptr(self.prepared()), ptr(out), out.stride(0), 1 if head else 0, ptr(extra), float(c0), float(c1), M,
              _stream())
         return out
@@ -812,19 +790,13 @@ class BatchNormalization(KerasModule):
             for name, p in self.keras_weights().items():
                 p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(-1))
 
-    def _invalidate(self):
-        self._aff_key = None  # statistics / affine moved through raw pointers (training)
-
     def affine(self):
         """(inv, shift) = (gamma rsqrt(var + eps), beta - mean inv), cached per
         parameter version (inference calls launch no elementwise kernels)."""
-        ps = (self.gamma, self.beta, self.moving_mean, self.moving_variance)
-        key = tuple((q._version, q.data_ptr()) for q in ps)
-        if getattr(self, "_aff_key", None) != key:
+        def build():
             inv = torch.rsqrt(self.moving_variance + self.epsilon) * self.gamma
-            self._aff = (inv, self.beta - self.moving_mean * inv)
-            self._aff_key = key
-        return self._aff
+            return inv, self.beta - self.moving_mean * inv
+        return self._packed("affine", (self.gamma, self.beta, self.moving_mean, self.moving_variance), build)
 
     def forward(self, x, out=None):
         if self.gamma is None:
@@ -891,23 +863,17 @@ class Attention(KerasModule):
         return (self.activation == "prelu" and self.out_kernel is not None and len(self.hidden_units) == 2
                 and k in (4, 8, 16) and self.hidden_units[0] <= 128 and self.hidden_units[1] <= 64)
 
-    def _invalidate(self):
-        self._ids_key = None  # weights moved through raw pointers (training): repack
-
     def prepared_ids(self, k):
         params = list(self.kernels) + list(self.biases) + list(self.alphas) + [self.out_kernel, self.out_bias]
-        key = (k, self.T) + tuple((p._version, p.data_ptr()) for p in params)
-        if getattr(self, "_ids_key", None) != key:
+
+        def build():
             h1, h2 = self.hidden_units
-            n = _lib.lib().rs_din_prepared_size(self.T, k, h1, h2)
-            if n < 0:
-                _lib.check(-1, "rs_din_prepared_size")
-            prep = torch.empty(n, dtype=torch.float32, device=self._dev)
+            prep = sized("rs_din_prepared_size", self.T, k, h1, h2, device=self._dev)
             call("rs_din_prepare", ptr(self.kernels[0]), ptr(self.biases[0]), ptr(self.alphas[0]), h1,
                  ptr(self.kernels[1]), ptr(self.biases[1]), ptr(self.alphas[1]), h2, ptr(self.out_kernel),
                  ptr(self.out_bias), self.T, k, ptr(prep), _stream())
-            self._ids_prep, self._ids_key = prep, key
-        return self._ids_prep
+            return prep
+        return self._packed("ids", params, build, extra=(k, self.T))
 
     def forward_ids(self, table, vocab, hist, cand, err=None, out=None, scores=None, cand_out=None):
         """Attention over key = value = table[hist], query = table[cand],
@@ -977,13 +943,13 @@ class Attention(KerasModule):
         s = _stream()
         if self.activation == "prelu" and not self.fused_ok(k):
             n = len(self.hidden_units)
-            hid = (C.c_int * max(n, 1))(*self.hidden_units)
+            hid = ints(self.hidden_units)
             wsz = _lib.lib().rs_din_attention_gen_workspace_size(B, T, k, n, hid)
             if wsz < 0:
                 _lib.check(-1, "rs_din_attention_gen_workspace_size")
             ws = scratch(self, "_gen_ws", wsz)
-            pa = lambda ts: (C.c_void_p * max(n, 1))(*[ptr(t) for t in ts])
-            call("rs_din_attention_gen_fwd", ptr(q), ptr(key), ptr(value), ptr(mask), T, k, n, hid, pa(self.kernels), pa(self.biases), pa(self.alphas),
+            call("rs_din_attention_gen_fwd", ptr(q), ptr(key), ptr(value), ptr(mask), T, k, n, hid,
+                 ptrs(self.kernels), ptrs(self.biases), ptrs(self.alphas),
                  ptr(self.out_kernel), ptr(self.out_bias), ptr(out), B, ptr(ws), ws.numel(), s)
         elif self.activation == "prelu":
             h1, h2 = self.hidden_units
@@ -1189,8 +1155,7 @@ _RES_MAXH, _RES_MAXU = 4, 16  # res_tower.hip RES_MAXH / RES_MAXU
 
 
 def _res_ok(d, hidden, n_units):
-    return bool(_lib.lib().rs_res_tower_ok(int(d), len(hidden), (C.c_int * max(len(hidden), 1))(*hidden),
-                                           int(n_units)))
+    return bool(_lib.lib().rs_res_tower_ok(int(d), len(hidden), ints(hidden), int(n_units)))
 
 
 def _res_prepare(units, head, device):
@@ -1198,21 +1163,17 @@ def _res_prepare(units, head, device):
     with equal widths, optionally with the model's Dense(1) head."""
     d, hidden = units[0].input_dim, units[0].hidden_units
     nh, nu = len(hidden), len(units)
-    ci = (C.c_int * nh)(*hidden)
-    size = _lib.lib().rs_res_tower_prepared_size(d, nh, ci, nu, 1 if head is not None else 0)
-    if size < 0:
-        _lib.check(-1, "rs_res_tower_prepared_size")
+    ci = ints(hidden)
+    prep = sized("rs_res_tower_prepared_size", d, nh, ci, nu, 1 if head is not None else 0, device=device)
     layers = [l for u in units for l in u._layers()]
-    pa = lambda ts: (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
-    prep = torch.empty(size, dtype=torch.float32, device=device)
-    call("rs_res_tower_prepare", d, nh, ci, nu, pa([l.kernel for l in layers]), pa([l.bias for l in layers]),
+    call("rs_res_tower_prepare", d, nh, ci, nu, ptrs([l.kernel for l in layers]), ptrs([l.bias for l in layers]),
          ptr(head.kernel) if head is not None else None, ptr(head.bias) if head is not None else None, ptr(prep),
          _stream())
     return prep
 
 
-def _res_key(layers):
-    return tuple((p._version, p.data_ptr()) for l in layers for p in (l.kernel, l.bias))
+def _res_params(layers):
+    return [p for l in layers for p in (l.kernel, l.bias)]
 
 
 class ResLayer(KerasModule):
@@ -1251,9 +1212,6 @@ class ResLayer(KerasModule):
     def _layers(self):
         return list(self.dense_layer) + [self.output_layer]
 
-    def _invalidate(self):
-        self.__dict__.pop("_res_prep", None)
-
     def keras_weights(self):
         if not self.built:
             raise RuntimeError("ResLayer: not built (call build(d) or run a forward first)")
@@ -1278,11 +1236,7 @@ class ResLayer(KerasModule):
 
     def prepared(self):
         """Weights packed for rs_res_tower_fwd, cached until a weight changes."""
-        key = _res_key(self._layers())
-        ent = self.__dict__.get("_res_prep")
-        if ent is None or ent[0] != key:
-            ent = self.__dict__["_res_prep"] = (key, _res_prepare([self], None, self._dev))
-        return ent[1]
+        return self._packed("res", _res_params(self._layers()), lambda: _res_prepare([self], None, self._dev))
 
     def forward_layers(self, x):
         """The per-layer composition: rs_dense_fwd per Dense, torch add / relu."""
@@ -1303,7 +1257,7 @@ class ResLayer(KerasModule):
             return self.forward_layers(x)
         out = torch.empty(B, d, dtype=torch.float32, device=self._dev)
         nh = len(self.hidden_units)
-        call("rs_res_tower_fwd", ptr(x), x.stride(0), d, nh, (C.c_int * nh)(*self.hidden_units), 1,
+        call("rs_res_tower_fwd", ptr(x), x.stride(0), d, nh, ints(self.hidden_units), 1,
              ptr(self.prepared()), 0, ptr(out), out.stride(0), B, _stream())
         return out
 
@@ -1317,8 +1271,7 @@ def _mmoe_dims(hidden, towers):
 
 
 def _mmoe_ok(d, hidden, n_experts, n_tasks, dims):
-    return bool(_lib.lib().rs_mmoe_ok(int(d), int(hidden), int(n_experts), int(n_tasks), len(dims) - 1,
-                                      (C.c_int * len(dims))(*dims)))
+    return bool(_lib.lib().rs_mmoe_ok(int(d), int(hidden), int(n_experts), int(n_tasks), len(dims) - 1, ints(dims)))
 
 
 def _mmoe_params(layer, towers):
@@ -1333,16 +1286,12 @@ def _mmoe_prepare(layer, towers, device):
     d, H, E, T = layer.input_dim, layer.hidden_units, layer.num_experts, layer.num_tasks
     dims = _mmoe_dims(H, towers)
     L = len(dims) - 1
-    ci = (C.c_int * len(dims))(*dims)
-    size = _lib.lib().rs_mmoe_prepared_size(d, H, E, T, L, ci)
-    if size < 0:
-        _lib.check(-1, "rs_mmoe_prepared_size")
-    pa = lambda ts: (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
+    ci = ints(dims)
+    prep = sized("rs_mmoe_prepared_size", d, H, E, T, L, ci, device=device)
     tl = [l for tw in towers for l in tw._layers()]
-    prep = torch.empty(size, dtype=torch.float32, device=device)
-    call("rs_mmoe_prepare", d, H, E, T, ptr(layer.expert_matrix), ptr(layer.expert_bias), pa(layer.gate_matrix),
-         pa(layer.gate_bias) if layer.gate_bias else None, L, ci, pa([l.kernel for l in tl]) if tl else None,
-         pa([l.bias for l in tl]) if tl else None, ptr(prep), _stream())
+    call("rs_mmoe_prepare", d, H, E, T, ptr(layer.expert_matrix), ptr(layer.expert_bias), ptrs(layer.gate_matrix),
+         ptrs(layer.gate_bias) if layer.gate_bias else None, L, ci, ptrs([l.kernel for l in tl]) if tl else None,
+         ptrs([l.bias for l in tl]) if tl else None, ptr(prep), _stream())
     return prep
 
 
@@ -1422,27 +1371,20 @@ class mmoe_layer(KerasModule):
             raise RuntimeError("mmoe_layer: not built (call build(d) or run a forward first)")
         return super().keras_weights()
 
-    def _invalidate(self):
-        self.__dict__.pop("_mmoe_prep", None)
-
     def fused_ok(self):
         H = self.hidden_units
         return self.built and _mmoe_ok(self.input_dim, H, self.num_experts, self.num_tasks, [H])
 
     def prepared(self):
         """Weights packed for rs_mmoe_fwd without towers, cached until a weight changes."""
-        key = tuple((p._version, p.data_ptr()) for p in _mmoe_params(self, []))
-        ent = self.__dict__.get("_mmoe_prep")
-        if ent is None or ent[0] != key:
-            ent = self.__dict__["_mmoe_prep"] = (key, _mmoe_prepare(self, [], self._dev))
-        return ent[1]
+        return self._packed("mmoe", _mmoe_params(self, []), lambda: _mmoe_prepare(self, [], self._dev))
 
     def forward_fused(self, x):
         """mmoe_layer.call as one launch: the mixes [B, T * H]."""
         B, d = x.shape
         H, E, T = self.hidden_units, self.num_experts, self.num_tasks
         mix = torch.empty(B, T * H, dtype=torch.float32, device=self._dev)
-        call("rs_mmoe_fwd", ptr(x), x.stride(0), d, H, E, T, 0, (C.c_int * 1)(H), None, ptr(self.prepared()), ptr(mix),
+        call("rs_mmoe_fwd", ptr(x), x.stride(0), d, H, E, T, 0, ints([H]), None, ptr(self.prepared()), ptr(mix),
              mix.stride(0), None, 0, 0, B, _stream())
         return mix
 
@@ -1648,38 +1590,24 @@ class _Recurrent(KerasModule):
             raise RuntimeError(f"{type(self).__name__}: not built (call build(input_dim) or run a forward first)")
         return super().keras_weights()
 
-    def _invalidate(self):
-        self.__dict__.pop("_rnn_prep", None)
-        self.__dict__.pop("_rnn_prep_bwd", None)
-
     def prepared(self):
         ps = [p for p in (self.kernel, self.recurrent_kernel, self.bias) if p is not None]
-        key = tuple((p._version, p.data_ptr()) for p in ps)
-        ent = self.__dict__.get("_rnn_prep")
-        if ent is None or ent[0] != key:
-            size = _lib.lib().rs_gru_prepared_size(self.input_dim, self.units)
-            if size < 0:
-                _lib.check(-1, "rs_gru_prepared_size")
-            prep = torch.empty(size, dtype=torch.float32, device=self._dev)
+
+        def build():
+            prep = sized("rs_gru_prepared_size", self.input_dim, self.units, device=self._dev)
             call("rs_gru_prepare", self.input_dim, self.units, ptr(self.kernel), ptr(self.recurrent_kernel),
                  ptr(self.bias), ptr(prep), _stream())
-            ent = self.__dict__["_rnn_prep"] = (key, prep)
-        return ent[1]
+            return prep
+        return self._packed("rnn", ps, build)
 
     def prepared_bwd(self):
         """The transposed recurrent kernel packed for rs_gru_bwd / rs_augru_bwd
         (rs_gru_prepare_bwd), cached per weight version."""
-        p = self.recurrent_kernel
-        key = (p._version, p.data_ptr())
-        ent = self.__dict__.get("_rnn_prep_bwd")
-        if ent is None or ent[0] != key:
-            size = _lib.lib().rs_gru_bwd_prepared_size(self.units)
-            if size < 0:
-                _lib.check(-1, "rs_gru_bwd_prepared_size")
-            prep = torch.empty(size, dtype=torch.float32, device=self._dev)
-            call("rs_gru_prepare_bwd", self.units, ptr(p), ptr(prep), _stream())
-            ent = self.__dict__["_rnn_prep_bwd"] = (key, prep)
-        return ent[1]
+        def build():
+            prep = sized("rs_gru_bwd_prepared_size", self.units, device=self._dev)
+            call("rs_gru_prepare_bwd", self.units, ptr(self.recurrent_kernel), ptr(prep), _stream())
+            return prep
+        return self._packed("rnn_bwd", (self.recurrent_kernel,), build)
 
     def _input(self, inputs):
         x = _seq_input(inputs, self._dev, type(self).__name__)
@@ -2043,12 +1971,8 @@ class InterestEvolution(KerasModule):
                     p.copy_(torch.as_tensor(weights[name], dtype=torch.float32).reshape(p.shape))
         self._weights_changed()
 
-    def _invalidate(self):
-        self.__dict__.pop("_dien_prep", None)
-
     def _hidden(self):
-        h = self.attention.att_hidden_units
-        return (C.c_int * max(len(h), 1))(*h)
+        return ints(self.attention.att_hidden_units)
 
     def fused_ok(self, T):
         a = self.attention
@@ -2058,26 +1982,21 @@ class InterestEvolution(KerasModule):
 
     def prepared(self):
         """The weights packed for the one-launch form (rs_dien_prepare), cached until one changes."""
-        key = tuple((p._version, p.data_ptr()) for p in self.keras_weights().values())
-        ent = self.__dict__.get("_dien_prep")
-        if ent is None or ent[0] != key:
+        def build():
             a, la = self.attention, self.attention.local_att
             n, D = len(a.att_hidden_units), self.embedding_size
-            size = _lib.lib().rs_dien_prepared_size(D, n, self._hidden())
-            if size < 0:
-                _lib.check(-1, "rs_dien_prepared_size")
-            pa = lambda ts: (C.c_void_p * n)(*[ptr(t) for t in ts])
+            prep = sized("rs_dien_prepared_size", D, n, self._hidden(), device=self._dev)
             ls = list(la.dnn.layers)
             dice = a.att_activation == "dice"
-            prep = torch.empty(size, dtype=torch.float32, device=self._dev)
             call("rs_dien_prepare", D, ptr(self.gru1.kernel), ptr(self.gru1.recurrent_kernel), ptr(self.gru1.bias),
                  ptr(self.gru2.cell.kernel), ptr(self.gru2.cell.recurrent_kernel), n, self._hidden(),
-                 _DIEN_ACTS[a.att_activation], pa([l.kernel for l in ls]), pa([l.bias for l in ls]),
-                 pa([l.dice.moving_mean for l in ls]) if dice else None,
-                 pa([l.dice.moving_variance for l in ls]) if dice else None,
-                 pa([l.dice.alphas for l in ls]) if dice else None, ptr(la.kernel), ptr(la.bias), ptr(prep), _stream())
-            ent = self.__dict__["_dien_prep"] = (key, prep)
-        return ent[1]
+                 _DIEN_ACTS[a.att_activation], ptrs([l.kernel for l in ls]), ptrs([l.bias for l in ls]),
+                 ptrs([l.dice.moving_mean for l in ls]) if dice else None,
+                 ptrs([l.dice.moving_variance for l in ls]) if dice else None,
+                 ptrs([l.dice.alphas for l in ls]) if dice else None, ptr(la.kernel), ptr(la.bias), ptr(prep),
+                 _stream())
+            return prep
+        return self._packed("dien", list(self.keras_weights().values()), build)
 
     def _outputs(self, B, T, out, want_h1, want_scores):
         D = self.embedding_size
@@ -2128,11 +2047,10 @@ class InterestEvolution(KerasModule):
         L = _lengths(seq_length, self._dev, B)
         out, h1, sc = self._outputs(B, T, out, want_h1, want_scores)
         err = err if err is not None else _ErrFlag(self._dev)
-        ia = lambda v: (C.c_int * n)(*v)
         la = lambda v: (C.c_int64 * n)(*v)
-        pa = lambda ts: (C.c_void_p * n)(*[ptr(t) for t in ts])
-        call("rs_dien_evolution_ids_fwd", n, ia([t.shape[1] for t in tables]), ia([_lib.id_kind(h) for h in hs]),
-             pa(hs), la([h.stride(0) for h in hs]), pa(cs), la([1] * n), pa(tables), la([t.shape[0] for t in tables]),
+        call("rs_dien_evolution_ids_fwd", n, ints([t.shape[1] for t in tables]), ints([_lib.id_kind(h) for h in hs]),
+             ptrs(hs), la([h.stride(0) for h in hs]), ptrs(cs), la([1] * n), ptrs(tables),
+             la([t.shape[0] for t in tables]),
              ptr(L), _lib.id_kind(L), *self._tail_args(T), ptr(h1), ptr(sc), ptr(out), out.stride(0), B, ptr(err.t),
              _stream())
         if check_ids:
@@ -2275,15 +2193,13 @@ def seq_pool_arrays(feats):
     source, table or None, lengths or None, mask or None)]: source = ids [B, T]
     with a table, embedded values [B, T, E] without."""
     n = len(feats)
-    ci = lambda v: (C.c_int * n)(*v)
-    cp = lambda v: (C.c_void_p * n)(*v)
     cl = lambda v: (C.c_int64 * n)(*v)
     kinds = [-1 if f[5] is None else _lib.id_kind(f[4]) for f in feats]
-    return (ci([f[0] for f in feats]), ci([f[1] for f in feats]), ci([f[2] for f in feats]),
-            ci([_COMBINERS[f[3]] for f in feats]), ci(kinds), cp([ptr(f[4]) for f in feats]),
-            cl([f[4].stride(0) for f in feats]), cp([ptr(f[5]) for f in feats]),
-            cl([0 if f[5] is None else f[5].shape[0] for f in feats]), cp([ptr(f[6]) for f in feats]),
-            ci([0 if f[6] is None else _lib.id_kind(f[6]) for f in feats]), cp([ptr(f[7]) for f in feats]))
+    return (ints([f[0] for f in feats]), ints([f[1] for f in feats]), ints([f[2] for f in feats]),
+            ints([_COMBINERS[f[3]] for f in feats]), ints(kinds), ptrs([f[4] for f in feats]),
+            cl([f[4].stride(0) for f in feats]), ptrs([f[5] for f in feats]),
+            cl([0 if f[5] is None else f[5].shape[0] for f in feats]), ptrs([f[6] for f in feats]),
+            ints([0 if f[6] is None else _lib.id_kind(f[6]) for f in feats]), ptrs([f[7] for f in feats]))
 
 
 def seq_pool(feats, out, B, err):

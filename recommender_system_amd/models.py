@@ -49,12 +49,12 @@ import ctypes as C
 import torch
 
 from . import _lib, _train_ops
-from ._lib import call, ptr
+from ._lib import call, ints, ptr, ptrs, sized
 from .layers import (AFMLayer, Attention, BatchNormalization, CrossLayer, Dense, DNNLayer, EmbedLayer, FFMLayer,
                      FGCNNLayer, FMLayer, InnerProductLayer, OuterProductLayer,
                      KerasModule, ResLayer, TowerMixin, WideLayer, sigmoid_combine, _ids_tensor, _to_device_f32,
-                     _AFM_MODES, _ErrFlag, _RES_MAXH, _RES_MAXU, _res_key, _res_ok, _res_prepare, mmoe_layer, tower_layer,
-                     _MMOE_MAXL, _mmoe_dims, _mmoe_input, _mmoe_ok, _mmoe_params, _mmoe_prepare,
+                     _AFM_MODES, _ErrFlag, _RES_MAXH, _RES_MAXU, _res_params, _res_ok, _res_prepare, mmoe_layer,
+                     tower_layer, _MMOE_MAXL, _mmoe_dims, _mmoe_input, _mmoe_ok, _mmoe_params, _mmoe_prepare,
                      DNN, InterestEvolution, PredictionLayer, _glorot_normal)
 from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, build_input_features
 
@@ -250,8 +250,7 @@ class DeepFM(KerasModule):
         if not self.dnn.tower_ok():
             return False
         dims = self.dnn._dims()
-        return bool(_lib.lib().rs_deepfm_fused_ok(self.nd, e.n_fields, e.k, self.fm.k, len(dims) - 1,
-                                                   (C.c_int * len(dims))(*dims)))
+        return bool(_lib.lib().rs_deepfm_fused_ok(self.nd, e.n_fields, e.k, self.fm.k, len(dims) - 1, ints(dims)))
 
     def forward_fused(self, inputs, check_ids=True, fm_logit=None):
         """DeepFM.call as ONE kernel (rs_deepfm_fwd)."""
@@ -267,7 +266,7 @@ class DeepFM(KerasModule):
         hoff, hvoc = e.host_meta()
         call("rs_deepfm_fwd_hm", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense), dense.stride(0), self.nd,
              ptr(e.table), ptr(e.field_offsets), ptr(e.field_vocab), hoff, hvoc, e.n_fields, e.k, ptr(prep),
-             ptr(self.fm.w0), self.fm.k, n, (C.c_int * (n + 1))(*dims), (C.c_int * n)(*acts), ptr(mlp), 0.5, 0.5,
+             ptr(self.fm.w0), self.fm.k, n, ints(dims), ints(acts), ptr(mlp), 0.5, 0.5,
              ptr(out), ptr(fm_logit), B, ptr(self._err.t), _lib.stream())
         if check_ids:
             self._err.check("DeepFM")
@@ -327,9 +326,6 @@ class DCN(KerasModule):
         if check_ids:
             self._err.check("DCN")
         return out
-
-    def _invalidate(self):
-        self._fused_key = None
 
     def train_step(self, inputs, labels, lr=0.01, return_loss=False, check_ids=True, dropout=None):
         """One step of compile_fit on DCN (model/dcn.py:24-34, utils/compile_fit.py:
@@ -405,7 +401,7 @@ class DCN(KerasModule):
         dims = [self.d] + [l.units for l in hidden] + [1]
         e = self.embed_layer
         return bool(_lib.lib().rs_dcn_fused_ok(self.nd, e.n_fields, e.k, self.cross_layer.layer_num, len(dims) - 1,
-                                                (C.c_int * len(dims))(*dims)))
+                                                ints(dims)))
 
     def _fused_params(self):
         """Cross image over [w_0..w_{L-1}, w_o[:d]] and the DNN tower with its
@@ -415,16 +411,14 @@ class DCN(KerasModule):
         cl = self.cross_layer
         params = list(cl.cross_weight) + list(cl.cross_bias) + [out.kernel, out.bias, last.kernel, last.bias] + \
             [p for l in hidden for p in (l.kernel, l.bias, l.alpha) if p is not None]
-        key = tuple((p._version, p.data_ptr()) for p in params)
-        if getattr(self, "_fused_key", None) == key:
-            return self._fused
         d = self.d
-        with torch.no_grad():
+
+        @torch.no_grad()
+        def build():
             L = cl.layer_num
             W = torch.cat([w.reshape(1, d) for w in cl.cross_weight] + [out.kernel[:d].reshape(1, d)]).contiguous()
             Bb = torch.cat([b.reshape(1, d) for b in cl.cross_bias] + [torch.zeros(1, d, device=self._dev)]).contiguous()
-            n = _lib.lib().rs_cross_prepared_size(d, L + 1)
-            cross = torch.empty(n, dtype=torch.float32, device=self._dev)
+            cross = sized("rs_cross_prepared_size", d, L + 1, device=self._dev)
             call("rs_cross_prepare", ptr(W), ptr(Bb), d, L + 1, ptr(cross), _lib.stream())
             # fold on rs_dense_fwd: wf = last.kernel @ wo2, bf = last.bias @ wo2 + out.bias
             wo2 = out.kernel[d:].reshape(-1, 1).contiguous()          # [out_dim, 1]
@@ -440,15 +434,12 @@ class DCN(KerasModule):
             bs = [l.bias for l in hidden] + [bf.contiguous()]
             als = [l.alpha for l in hidden] + [None]
             dims = [d] + [l.units for l in hidden] + [1]
-            nl = len(ks)
-            ci = (C.c_int * (nl + 1))(*dims)
-            pa = lambda ts: (C.c_void_p * nl)(*[ptr(t) for t in ts])
-            mlp = torch.empty(_lib.lib().rs_mlp_prepared_size(nl, ci), dtype=torch.float32, device=self._dev)
-            call("rs_mlp_prepare", nl, ci, pa(ks), pa(bs), pa(als), None, ptr(mlp), _lib.stream())
+            nl, ci = len(ks), ints(dims)
+            mlp = sized("rs_mlp_prepared_size", nl, ci, device=self._dev)
+            call("rs_mlp_prepare", nl, ci, ptrs(ks), ptrs(bs), ptrs(als), None, ptr(mlp), _lib.stream())
             acts = [_lib.ACT[l.activation] for l in hidden] + [0]
-        self._fused = (cross, mlp, dims, acts, (W, Bb, wf, bf))
-        self._fused_key = key
-        return self._fused
+            return cross, mlp, dims, acts, (W, Bb, wf, bf)
+        return self._packed("dcn", params, build)
 
     def forward_fused(self, inputs, check_ids=True):
         """DCN.call as ONE kernel (rs_dcn_fwd)."""
@@ -461,7 +452,7 @@ class DCN(KerasModule):
         hoff, hvoc = e.host_meta()
         call("rs_dcn_fwd_hm", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense), dense.stride(0), self.nd,
              ptr(e.table), ptr(e.field_offsets), ptr(e.field_vocab), hoff, hvoc, e.n_fields, e.k,
-             self.cross_layer.layer_num, ptr(cross), n, (C.c_int * (n + 1))(*dims), (C.c_int * n)(*acts), ptr(mlp),
+             self.cross_layer.layer_num, ptr(cross), n, ints(dims), ints(acts), ptr(mlp),
              ptr(out), B, ptr(self._err.t), _lib.stream())
         if check_ids:
             self._err.check("DCN")
@@ -759,7 +750,7 @@ class DIN(TowerMixin, KerasModule):
         ls = self._layers()
         n = len(ls)
         dims = self._dims()
-        cdims = (C.c_int * (n + 1))(*dims)
+        cdims = ints(dims)
         if T != att.T or not _lib.lib().rs_din_forward_ids_supported(T, K, h1, h2, n, cdims):
             return None
         if self.bn_layer.gamma is None:
@@ -771,7 +762,7 @@ class DIN(TowerMixin, KerasModule):
         arr = lambda ctype, vals: (ctype * k)(*vals)
         call("rs_din_forward_ids", ptr(hist), _lib.id_kind(hist), hist.stride(0), ptr(cand), cand.stride(0), T, K,
              ptr(seq_layer.table), int(seq_layer.vocab_sizes[0]), h1, h2, ptr(att.prepared_ids(K)), None, 0,
-             ptr(sc), ptr(sh), n, cdims, (C.c_int * n)(*[_lib.ACT[l.activation] for l in ls]),
+             ptr(sc), ptr(sh), n, cdims, ints([_lib.ACT[l.activation] for l in ls]),
              ptr(self.prepared()), ptr(y), y.stride(0), k, arr(C.c_int, [p[0] for p in pieces]),
              arr(C.c_int, [p[1] for p in pieces]), arr(C.c_int, [p[2] for p in pieces]),
              arr(C.c_void_p, [ptr(p[3]) for p in pieces]), arr(C.c_int64, [p[3].stride(0) for p in pieces]),
@@ -812,8 +803,8 @@ class DIN(TowerMixin, KerasModule):
         sc, sh = affine
         k = len(pieces)
         arr = lambda ctype, vals: (ctype * k)(*vals)
-        call("rs_mlp_affine_pieces_fwd", ptr(emb), emb.stride(0), ptr(sc), ptr(sh), n, (C.c_int * (n + 1))(*dims),
-             (C.c_int * n)(*[_lib.ACT[l.activation] for l in ls]), ptr(self.prepared()), ptr(out), out.stride(0), 0,
+        call("rs_mlp_affine_pieces_fwd", ptr(emb), emb.stride(0), ptr(sc), ptr(sh), n, ints(dims),
+             ints([_lib.ACT[l.activation] for l in ls]), ptr(self.prepared()), ptr(out), out.stride(0), 0,
              None, 1.0, 1.0, B, k, arr(C.c_int, [p[0] for p in pieces]), arr(C.c_int, [p[1] for p in pieces]),
              arr(C.c_int, [p[2] for p in pieces]), arr(C.c_void_p, [ptr(p[3]) for p in pieces]),
              arr(C.c_int64, [p[3].stride(0) for p in pieces]),
@@ -1329,10 +1320,6 @@ class DeepCrossing(KerasModule):
         _set_prefixed(self.output_layer, "output_layer", weights, strict)
         self._weights_changed()
 
-    def _invalidate(self):
-        self.__dict__.pop("_res_prep", None)
-        self.__dict__.pop("_res_prep_bwd", None)
-
     def _all_layers(self):
         return [l for unit in self.res_layer for l in unit._layers()] + [self.output_layer]
 
@@ -1345,11 +1332,8 @@ class DeepCrossing(KerasModule):
     def prepared(self):
         """Every unit's weights and the head packed for rs_deepcrossing_fwd,
         cached until a weight changes."""
-        key = _res_key(self._all_layers())
-        ent = self.__dict__.get("_res_prep")
-        if ent is None or ent[0] != key:
-            ent = self.__dict__["_res_prep"] = (key, _res_prepare(list(self.res_layer), self.output_layer, self._dev))
-        return ent[1]
+        return self._packed("res", _res_params(self._all_layers()),
+                            lambda: _res_prepare(list(self.res_layer), self.output_layer, self._dev))
 
     def forward_fused(self, inputs, check_ids=True, x_last=None):
         """DeepCrossing.call as ONE kernel (rs_deepcrossing_fwd).  x_last
@@ -1361,7 +1345,7 @@ class DeepCrossing(KerasModule):
         out = torch.empty(B, 1, dtype=torch.float32, device=self._dev)
         call("rs_deepcrossing_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense) if self.nd else None,
              dense.stride(0) if self.nd else 0, self.nd, ptr(e.table), ptr(e.field_offsets), ptr(e.field_vocab),
-             e.n_fields, e.k, nh, (C.c_int * nh)(*self.hidden_units), len(self.res_layer), ptr(self.prepared()),
+             e.n_fields, e.k, nh, ints(self.hidden_units), len(self.res_layer), ptr(self.prepared()),
              ptr(out), ptr(x_last), 0 if x_last is None else x_last.stride(0), B, ptr(self._err.t), _lib.stream())
         if check_ids:
             self._err.check("DeepCrossing")
@@ -1384,21 +1368,14 @@ class DeepCrossing(KerasModule):
         """The backward weight image (rs_res_tower_prepare_bwd: every unit's
         kernels transposed, last unit first, and the head's kernel), cached
         under the key of ``prepared``."""
-        key = _res_key(self._all_layers())
-        ent = self.__dict__.get("_res_prep_bwd")
-        if ent is None or ent[0] != key:
+        def build():
             nh, nu = len(self.hidden_units), len(self.res_layer)
-            ci = (C.c_int * nh)(*self.hidden_units)
-            size = _lib.lib().rs_res_tower_bwd_prepared_size(self.d, nh, ci, nu)
-            if size < 0:
-                _lib.check(-1, "rs_res_tower_bwd_prepared_size")
-            kernels = [l.kernel for l in self._all_layers()[:-1]]
-            img = torch.empty(size, dtype=torch.float32, device=self._dev)
-            call("rs_res_tower_prepare_bwd", self.d, nh, ci, nu,
-                 (C.c_void_p * len(kernels))(*[ptr(t) for t in kernels]), ptr(self.output_layer.kernel), ptr(img),
-                 _lib.stream())
-            ent = self.__dict__["_res_prep_bwd"] = (key, img)
-        return ent[1]
+            ci = ints(self.hidden_units)
+            img = sized("rs_res_tower_bwd_prepared_size", self.d, nh, ci, nu, device=self._dev)
+            call("rs_res_tower_prepare_bwd", self.d, nh, ci, nu, ptrs([l.kernel for l in self._all_layers()[:-1]]),
+                 ptr(self.output_layer.kernel), ptr(img), _lib.stream())
+            return img
+        return self._packed("res_bwd", _res_params(self._all_layers()), build)
 
     def train_step(self, inputs, labels, lr=0.01, return_loss=False, check_ids=True, fused=None):
         """One step of compile_fit (utils/compile_fit.py:9-15: SGD(lr), binary
@@ -1433,7 +1410,7 @@ class DeepCrossing(KerasModule):
         all_layers = self._all_layers()
         gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in all_layers]))
         if fused:
-            ci = (C.c_int * nh)(*self.hidden_units)
+            ci = ints(self.hidden_units)
             widths = self.hidden_units + [d]
             saved = emp(B * (d + nu * sum(widths)))
             deltas = emp(B * nu * sum(widths))
@@ -1724,10 +1701,6 @@ class MMOE(KerasModule):
             _set_prefixed(tower, f"tower_layer_{t}", weights, strict)
         self._weights_changed()
 
-    def _invalidate(self):
-        self.__dict__.pop("_mmoe_prep", None)
-        self.__dict__.pop("_mmoe_prep_bwd", None)
-
     def _dims(self):
         return _mmoe_dims(self.mmoe_layer.hidden_units, list(self.tower_layer))
 
@@ -1738,30 +1711,25 @@ class MMOE(KerasModule):
         dims = self._dims()
         return bool(m.built and self.activation in ("relu", "linear", None) and len(dims) - 1 <= _MMOE_MAXL
                     and _lib.lib().rs_mmoe_train_ok(m.input_dim, m.hidden_units, m.num_experts, m.num_tasks,
-                                                    len(dims) - 1, (C.c_int * len(dims))(*dims)))
+                                                    len(dims) - 1, ints(dims)))
 
     def prepared_bwd(self):
         """The backward weight image (rs_mmoe_prepare_bwd: every tower layer's
         kernels transposed, top layer first, and W1^T), cached under the key
         of ``prepared``."""
         towers = list(self.tower_layer)
-        key = tuple((p._version, p.data_ptr()) for p in _mmoe_params(self.mmoe_layer, towers))
-        ent = self.__dict__.get("_mmoe_prep_bwd")
-        if ent is None or ent[0] != key:
+
+        def build():
             m = self.mmoe_layer
             dims = self._dims()
-            n = len(dims) - 1
-            ci = (C.c_int * len(dims))(*dims)
-            size = _lib.lib().rs_mmoe_bwd_prepared_size(m.input_dim, m.hidden_units, m.num_experts, m.num_tasks, n, ci)
-            if size < 0:
-                _lib.check(-1, "rs_mmoe_bwd_prepared_size")
-            pa = lambda ts: (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
-            img = torch.empty(size, dtype=torch.float32, device=self._dev)
+            n, ci = len(dims) - 1, ints(dims)
+            img = sized("rs_mmoe_bwd_prepared_size", m.input_dim, m.hidden_units, m.num_experts, m.num_tasks, n, ci,
+                        device=self._dev)
             call("rs_mmoe_prepare_bwd", m.input_dim, m.hidden_units, m.num_experts, m.num_tasks, ptr(m.expert_matrix),
-                 pa(m.gate_matrix), n, ci, pa([l.kernel for tw in towers for l in tw._layers()]), ptr(img),
+                 ptrs(m.gate_matrix), n, ci, ptrs([l.kernel for tw in towers for l in tw._layers()]), ptr(img),
                  _lib.stream())
-            ent = self.__dict__["_mmoe_prep_bwd"] = (key, img)
-        return ent[1]
+            return img
+        return self._packed("mmoe_bwd", _mmoe_params(self.mmoe_layer, towers), build)
 
     def gradients(self, x, labels, loss_weights=None, fused=None, want_dx=False):
         """The gradients of one training step's loss without its l2 terms:
@@ -1809,12 +1777,9 @@ class MMOE(KerasModule):
         gw = gemm_ws(self, gemm_need([(d, HE, B), (d, E, B)] + [(*L.kernel.shape, B) for L in towers[0]]))
         grads = {}
         if fused:
-            ci = (C.c_int * (n + 1))(*dims)
-            ca = (C.c_int * n)(*([_lib.ACT[self.activation]] * (n - 1) + [0]))
-            size = _lib.lib().rs_mmoe_saved_size(d, H, E, T, n, ci, B)
-            if size < 0:
-                _lib.check(-1, "rs_mmoe_saved_size")
-            saved = emp(size)
+            ci = ints(dims)
+            ca = ints([_lib.ACT[self.activation]] * (n - 1) + [0])
+            saved = sized("rs_mmoe_saved_size", d, H, E, T, n, ci, B, device=dev)
             call("rs_mmoe_train_fwd", ptr(x), x.stride(0), d, H, E, T, n, ci, ca, ptr(self.prepared()), ptr(saved),
                  ptr(z), z.stride(0), z.stride(1), B, st)
             G, loss = mmoe_head(z, y, loss_weights, st)
@@ -1926,11 +1891,8 @@ class MMOE(KerasModule):
         """The layer's and every tower's weights packed for rs_mmoe_fwd,
         cached until a weight changes."""
         towers = list(self.tower_layer)
-        key = tuple((p._version, p.data_ptr()) for p in _mmoe_params(self.mmoe_layer, towers))
-        ent = self.__dict__.get("_mmoe_prep")
-        if ent is None or ent[0] != key:
-            ent = self.__dict__["_mmoe_prep"] = (key, _mmoe_prepare(self.mmoe_layer, towers, self._dev))
-        return ent[1]
+        return self._packed("mmoe", _mmoe_params(self.mmoe_layer, towers),
+                            lambda: _mmoe_prepare(self.mmoe_layer, towers, self._dev))
 
     def forward_fused(self, inputs, mix=None):
         """MMOE.call as ONE kernel.  mix (optional, [B, T * H]) receives the
@@ -1943,7 +1905,7 @@ class MMOE(KerasModule):
         acts = [_lib.ACT[self.activation]] * (n - 1) + [0]
         y = torch.empty(m.num_tasks, B, self.output_dim, dtype=torch.float32, device=self._dev)
         call("rs_mmoe_fwd", ptr(x), x.stride(0), d, m.hidden_units, m.num_experts, m.num_tasks, n,
-             (C.c_int * (n + 1))(*dims), (C.c_int * n)(*acts), ptr(self.prepared()), ptr(mix),
+             ints(dims), ints(acts), ptr(self.prepared()), ptr(mix),
              0 if mix is None else mix.stride(0), ptr(y), y.stride(0), y.stride(1), B, _lib.stream())
         return [y[t] for t in range(m.num_tasks)]
 
@@ -2143,11 +2105,9 @@ class DIEN(TowerMixin, KerasModule):
         for i in range(0, len(pieces) if B else 0, 16):
             ch = pieces[i:i + 16]
             n = len(ch)
-            call("rs_concat_pieces", n, (C.c_int * n)(*[p[0] for p in ch]), (C.c_int * n)(*[p[1] for p in ch]),
-                 (C.c_int * n)(*[-1 if p[3] is None else _lib.id_kind(p[2]) for p in ch]),
-                 (C.c_void_p * n)(*[ptr(p[2]) for p in ch]),
-                 (C.c_int64 * n)(*[p[2].stride(0) if p[3] is None else 1 for p in ch]),
-                 (C.c_void_p * n)(*[ptr(p[3]) for p in ch]),
+            call("rs_concat_pieces", n, ints([p[0] for p in ch]), ints([p[1] for p in ch]),
+                 ints([-1 if p[3] is None else _lib.id_kind(p[2]) for p in ch]), ptrs([p[2] for p in ch]),
+                 (C.c_int64 * n)(*[p[2].stride(0) if p[3] is None else 1 for p in ch]), ptrs([p[3] for p in ch]),
                  (C.c_int64 * n)(*[0 if p[3] is None else p[3].shape[0] for p in ch]), ptr(x), x.stride(0), B,
                  ptr(err.t), _lib.stream())
         for c, at in zip(self.pooled_cols, self._pooled_at):
