@@ -1800,7 +1800,11 @@ int rs_afm_train_fwd(const void* ids, int id_kind, int64_t id_stride,
  * `world` ranks in blocks of `rows_per_rank` (owner = row / rows_per_rank).
  *  rs_shard_bucketize: counts[r] = #lookups owned by rank r; perm[i] = the
  *   position of lookup i (= b*F + c) in owner-major order; send_rows[perm[i]]
- *   = local row index on the owner.  Stable within each owner.
+ *   = local row index on the owner.  Stable within each owner.  An id outside
+ *   [0, vocab) sets *err_flag and is kept as a lookup of owner 0 with local
+ *   row -1 (counted in counts[0], perm still a permutation of 0 .. n-1, its
+ *   send_rows word -1: rs_gather_rows serves it as a zero row), so the packed
+ *   exchange keeps one word and one row per lookup.
  *   workspace: rs_shard_workspace_size(batch*n_fields, world) bytes, device,
  *   zero-filled once when allocated (its tail holds the control words of the
  *   one-pass slotted kernel, which leaves them ready for the next call); one
@@ -1823,6 +1827,10 @@ int rs_shard_bucketize(const void* ids, int id_kind, int64_t id_stride,
  * owner's shard that no lookup reads); slot_of [B*F]: the slot of lookup
  * b*F+c, or -1 when its owner's slots overflowed (*overflow_flag set; redo the
  * step with the exact protocol) or its id is out of range (*err_flag set).
+ * An out-of-range id is no lookup of any owner: it takes no slot, writes no
+ * send word, is not counted in counts[] (counts[o] = the valid lookups of
+ * owner o, overflowed ones included) and cannot push a valid lookup past
+ * `cap`.
  * The returned rows are then addressed by slot_of as int32 ids of a single
  * [world*cap, k] table: rs_embed_fm_fwd(ids = slot_of, offsets 0, vocab
  * world*cap) computes the FM straight from the exchange buffer.

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(SH_THREADS) void shard_hist(ShardArgs a, int32_t* h
 }
 
 // counts[o] = sum_b hist[b][o]; hist[b][o] <- base(o) + sum_{b'<b} hist[b'][o]
-// base(o) = sum_{p<o} counts[p] (packed) or o * cap (slotted, cap > 0).
+// base(o) = sum_{p<o} counts[p].
 // One 256-thread workgroup: wave w owns owners w, w+4, ...; each owner's
 // column is reduced / scanned 64 blocks at a time (independent loads, a
 // wave-level inclusive scan, a running carry) — no serial per-block chain.
@@ -93,7 +93,7 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void shard_scan(int32_t* hist, int nblocks, int world, int32_t* counts, int cap) {
+__global__ __launch_bounds__(256) void shard_scan(int32_t* hist, int nblocks, int world, int32_t* counts) {
   __shared__ int tot[SH_MAXW];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int o = w; o < world; o += 4) {
@@ -109,9 +109,7 @@ __global__ __launch_bounds__(256) void shard_scan(int32_t* hist, int nblocks, in
   __syncthreads();
   for (int o = w; o < world; o += 4) {
     int carry = 0;
-    if (cap > 0) carry = o * cap;
-    else
-      for (int p = 0; p < o; ++p) carry += tot[p];
+    for (int p = 0; p < o; ++p) carry += tot[p];
     for (int b0 = 0; b0 < nblocks; b0 += 64) {
       const int b = b0 + lane;
       const int v = b < nblocks ? hist[(int64_t)b * world + o] : 0;
@@ -229,8 +227,10 @@ __global__ __launch_bounds__(SP_THREADS) void shard_slot_onepass(ShardArgs a, ui
     loc = -1;
     o = i < a.n ? shard_owner(a, i, loc) : -1;
   }
-  // stable in-block rank: peel one owner at a time per wave
-  const bool act = o >= 0;
+  // stable in-block rank: peel one owner at a time per wave.  An out-of-range
+  // id (shard_owner: owner 0, local -1) is no lookup of any owner: it takes no
+  // rank, no position and no part of counts
+  const bool act = o >= 0 && loc >= 0;
   int rank = 0;
   uint64_t todo = __ballot(act);
   while (todo) {
@@ -401,6 +401,7 @@ extern "C" int rs_shard_bucketize(const void* ids, int id_kind, int64_t id_strid
              "rs_shard_bucketize: bad shape (1 <= world <= %d)", SH_MAXW);
   RS_REQUIRE(batch * n_fields < ((int64_t)1 << 31), "rs_shard_bucketize: too many lookups");
   RS_REQUIRE(rows_per_rank < ((int64_t)1 << 31), "rs_shard_bucketize: shard rows must fit int32");
+  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_shard_bucketize: bad id_kind");
   hipStream_t st = as_stream(stream);
   ShardArgs a{ids, id_kind, id_stride, field_offsets, field_vocab, n_fields, batch * n_fields, rows_per_rank, world,
               err_flag, 1.0 / (double)rows_per_rank};
@@ -411,7 +412,7 @@ extern "C" int rs_shard_bucketize(const void* ids, int id_kind, int64_t id_strid
     return launch_status("rs_shard_bucketize");
   }
   shard_hist<<<nb, SH_THREADS, 0, st>>>(a, hist);
-  shard_scan<<<1, 256, 0, st>>>(hist, nb, world, counts, 0);
+  shard_scan<<<1, 256, 0, st>>>(hist, nb, world, counts);
   shard_place<<<nb, SH_THREADS, 0, st>>>(a, hist, perm, send_rows, 0, nullptr);
   return launch_status("rs_shard_bucketize");
 }
@@ -428,16 +429,14 @@ extern "C" int rs_shard_slot_bucketize(const void* ids, int id_kind, int64_t id_
   RS_REQUIRE(batch * n_fields < ((int64_t)1 << 31) && (int64_t)world * cap < ((int64_t)1 << 31),
              "rs_shard_slot_bucketize: too many lookups / slots");
   RS_REQUIRE(rows_per_rank < ((int64_t)1 << 31), "rs_shard_slot_bucketize: shard rows must fit int32");
+  RS_REQUIRE(id_kind >= RS_ID_I32 && id_kind <= RS_ID_F32, "rs_shard_slot_bucketize: bad id_kind");
   hipStream_t st = as_stream(stream);
   ShardArgs a{ids, id_kind, id_stride, field_offsets, field_vocab, n_fields, batch * n_fields, rows_per_rank, world,
               err_flag, 1.0 / (double)rows_per_rank};
-  const int nb = (int)((a.n + SH_CHUNK - 1) / SH_CHUNK);
-  int32_t* hist = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(workspace) + SH_CTRL_BYTES);
   if (a.n == 0) {
     (void)hipMemsetAsync(counts, 0, world * sizeof(int32_t), st);
     return launch_status("rs_shard_slot_bucketize");
   }
-  (void)hist;
   const int nbp = (int)((a.n + SP_PER - 1) / SP_PER);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   shard_slot_onepass<<<nbp, SP_THREADS, 0, st>>>(a, reinterpret_cast<uint64_t*>(ws + SH_CTRL_BYTES),
