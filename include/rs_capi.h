@@ -1584,6 +1584,58 @@ int rs_outer_product_w_grad(const float* emb, int64_t emb_stride,
                             const float* dout, int64_t dout_stride,
                             int n_fields, int k, int64_t batch, float* dW,
                             rs_stream_t stream);
+/* The product layers' backward past 64 fields (PNN with FGCNN: the layers see
+ * z = [embed | new fields], 83 fields at the defaults) — the counterpart of
+ * rs_product_fwd.  z [B, F, k] rows z_stride floats apart; dx = the DNN's
+ * input gradient, one row [dflat (F*k) | dinner (P, if inner) | douter (P, if
+ * outer)] per sample, dx_stride floats apart; W = the RAW [k, P, k] tensor
+ * (not the rs_outer_prepare image).  2 <= n_fields <= 128, 1 <= k <= 16.
+ * rs_product_bwd (outer iff W != NULL; inner = 0 and W = NULL is refused):
+ *  ONE launch WRITES dz[b,i,:] = dflat + sum_{j!=i} dinner_p(i,j) z_j +
+ *  sum_{j>i} g_p z_j W_p + sum_{j<i} g_p z_j W_p^T; one fp32 MFMA chain per
+ *  (sample tile, field) over the other fields in order, 16 samples per
+ *  workgroup, 8 or 4 where 16 rows of z pass 64 KB of LDS; no atomics.
+ * rs_product_w_grad (always outer; `inner` only places the douter columns):
+ *  dW[a,p,c] = sum_b g_bp z_j[b,a] z_i[b,c], one workgroup per pair.
+ * A refusal launches nothing; batch 0 returns RS_OK.                        */
+int rs_product_bwd(const float* z, int64_t z_stride, const float* dx,
+                   int64_t dx_stride, int n_fields, int k, int inner,
+                   const float* W, int64_t batch, float* dz, int64_t dz_stride,
+                   rs_stream_t stream);
+int rs_product_w_grad(const float* z, int64_t z_stride, const float* dx,
+                      int64_t dx_stride, int n_fields, int k, int inner,
+                      int64_t batch, float* dW, rs_stream_t stream);
+/* FGCNN conv stack backward (the layers of rs_fgcnn_conv_fwd, same
+ * configuration arguments), ONE launch for the stack plus a fixed-order finish
+ * of the weight gradients.  Saved from the forward: z[b, 0:F*k] (the rows) and
+ * ws (every layer's pooled map).  dws [B, ws_size] = dL/d(pooled maps) from
+ * the recombination Dense layers.  Per sample and layer, top down, in LDS: the
+ * pooled gradient (dws_i + the input gradient of the layer above) goes to the
+ * FIRST pool member attaining the maximum (members recomputed in fp32), times
+ * 1 - p^2 (p the saved pooled value); rows the pool dropped get zero.  Then
+ * db = sum dY, dW[t,c,n] = sum Xpad[h+t,d,c] dY[h,d,n], and dX = the
+ * transposed convolution.  dX_0 is ADDED into de[b, 0:F*k] (rows de_stride
+ * apart).  dconv_w[i] / dconv_b[i] (host arrays of device pointers, the
+ * parameters' shapes) are WRITTEN: per-workgroup partial rows in `workspace`
+ * (rs_fgcnn_conv_bwd_workspace_size bytes for this batch), summed in row
+ * order; no atomics, bitwise reproducible.
+ * rs_fgcnn_conv_bwd_workspace_size returns -1 (error string set) for a
+ * configuration rs_fgcnn_workspace_size refuses or whose backward tile — one
+ * layer's kernel, padded input map, padded dY map and the carried gradient —
+ * passes 128 KB of LDS (the defaults fit at k = 8, 16 and 32).              */
+int64_t rs_fgcnn_conv_bwd_workspace_size(int n_fields, int k, int n_layers,
+                                         const int* filters,
+                                         const int* kernel_width,
+                                         const int* pooling_width,
+                                         int64_t batch);
+int rs_fgcnn_conv_bwd(const float* z, int64_t z_stride, const float* ws,
+                      int64_t ws_stride, const float* dws, int64_t dws_stride,
+                      int n_fields, int k, int n_layers, const int* filters,
+                      const int* kernel_width, const int* pooling_width,
+                      const float* const* conv_w, float* de, int64_t de_stride,
+                      float* const* dconv_w, float* const* dconv_b,
+                      void* workspace, int64_t workspace_bytes, int64_t batch,
+                      rs_stream_t stream);
 /* DIN training (compile_fit on model/din.py:56-95, training=True; the host
  * layer DIN.train_step composes these with rs_dense_fwd / rs_gemm /
  * rs_col_sum / rs_sgd_update / rs_embedding_sgd):

@@ -185,6 +185,10 @@ SIGNATURES = {
     "rs_outer_product_bwd": (I, [P, L, P, L, P, I, I, L, P, L, P]),
     "rs_bi_interaction_bwd": (I, [P, L, P, L, I, I, L, P, L, P]),
     "rs_outer_product_w_grad": (I, [P, L, P, L, I, I, L, P, P]),
+    "rs_product_bwd": (I, [P, L, P, L, I, I, I, P, L, P, L, P]),
+    "rs_product_w_grad": (I, [P, L, P, L, I, I, I, L, P, P]),
+    "rs_fgcnn_conv_bwd_workspace_size": (L, [I, I, I, P, P, P, L]),
+    "rs_fgcnn_conv_bwd": (I, [P, L, P, L, P, L, I, I, I, P, P, P, P, P, L, P, P, P, L, L, P]),
     "rs_din_att_concat": (I, [P, P, L, I, I, P, P]),
     "rs_din_att_concat_bwd": (I, [P, P, P, L, I, I, P, L, P, P]),
     "rs_prelu_rows_fwd": (I, [P, L, I, P, I, P, P]),

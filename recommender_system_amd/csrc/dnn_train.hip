@@ -525,6 +525,81 @@ __global__ __launch_bounds__(256) void outer_w_grad_kernel(const float* __restri
   }
 }
 
+// ------------------------------- product layers' backward, 2..128 fields
+// rs_product_bwd: the backward of rs_product_fwd's [flat | inner | outer] row
+// in ONE launch, dz[b,i,:] = dflat + sum_j dinner_p(i,j) z_j + sum_p g_p (z_j
+// W_p | z_i W_p^T), on outer_bwd_kernel's mapping: a workgroup holds S <= 16
+// samples' z rows in LDS (S shrinks to the 64 KiB budget; MFMA rows past S
+// carry zeros), wave w owns fields f = w, w + 16, ... and runs ONE MFMA chain
+// per field over the other fields in order — per field o first the inner term
+// (A = dinner z_o, B = the identity) then the outer term (A = g z_o, B = W_p or
+// W_p^T from the raw [k, P, k] tensor).  dz is written, not accumulated.
+struct ProdBwd {
+  const float* z;
+  int64_t ldz;
+  const float* dx;  // the DNN's input gradient [dflat | dinner | douter]
+  int64_t ldx;
+  int64_t oi, oo;   // first column of dinner / douter, -1: absent
+  const float* W;
+  int F, k, S;
+  int64_t B;
+  float* dz;
+  int64_t lddz;
+};
+
+__global__ __launch_bounds__(1024) void product_bwd_kernel(ProdBwd a) {
+  extern __shared__ float se[];
+  const int F = a.F, k = a.k, S = a.S;
+  const int Fk = F * k, LS = Fk + 1, P = F * (F - 1) / 2;
+  const int64_t B = a.B, b0 = (int64_t)blockIdx.x * S;
+  for (int e = threadIdx.x; e < S * Fk; e += 1024) {
+    const int r = e / Fk, c = e - r * Fk;
+    const int64_t b = b0 + r < B ? b0 + r : B - 1;
+    se[r * LS + c] = a.z[b * a.ldz + c];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int s = lane & 15, kk = lane >> 4;
+  const bool vs = s < S && b0 + s < B;
+  const float* zs = se + (s < S ? s : 0) * LS;
+  const float* grow = a.dx + (vs ? b0 + s : b0) * a.ldx;
+  const float* W = a.W;
+  for (int f = w; f < F; f += 16) {
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int o = 0; o < F; ++o) {
+      if (o == f) continue;
+      const int p = o > f ? pair_of(f, o, F) : pair_of(o, f, F);
+      const float* eo = zs + o * k;
+      if (a.oi >= 0) {
+        const float gx = grow[a.oi + p];
+        const float g = vs ? gx : 0.f;
+        for (int k0 = 0; k0 < k; k0 += 4) {
+          const int kr = k0 + kk;
+          acc = mfma16x16x4(kr < k ? g * eo[kr] : 0.f, kr == s ? 1.f : 0.f, acc);
+        }
+      }
+      if (a.oo >= 0) {
+        const float gx = grow[a.oo + p];
+        const float g = vs ? gx : 0.f;
+        for (int k0 = 0; k0 < k; k0 += 4) {
+          const int kr = k0 + kk;
+          const float av = kr < k ? g * eo[kr] : 0.f;
+          // B[kr][col]: W[kr, p, col] (z_o W_p, o = j > f) or W[col, p, kr] (z_o W_p^T, o = i < f)
+          const int ac = s < k ? s : 0, ak = kr < k ? kr : 0;
+          const float wx = o > f ? W[((int64_t)ak * P + p) * k + ac] : W[((int64_t)ac * P + p) * k + ak];
+          acc = mfma16x16x4(av, (s < k && kr < k) ? wx : 0.f, acc);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int sr = 4 * kk + r;
+      const int64_t b = b0 + sr;
+      if (sr < S && b < B && s < k) a.dz[b * a.lddz + f * k + s] = a.dx[b * a.ldx + f * k + s] + acc[r];
+    }
+  }
+}
+
 // ------------------------------------------- NFM Bi-Interaction backward
 // model/nfm.py:28 on [B, F, k]: bi_c = 0.5((sum_f e_fc)^2 - sum_f e_fc^2) ->
 // de_fc = dbi_c (S_c - e_fc), S_c = sum_f e_fc (fields summed in order).
@@ -891,6 +966,62 @@ extern "C" int rs_outer_product_w_grad(const float* emb, int64_t emb_stride, con
   outer_w_grad_kernel<<<(unsigned)(n_fields * (n_fields - 1) / 2), 256, 0, as_stream(stream)>>>(
       emb, emb_stride, dout, dout_stride, n_fields, k, batch, dW);
   return launch_status("rs_outer_product_w_grad");
+}
+
+// rs_product_bwd / rs_product_w_grad: 2..128 fields, k <= 16, the mode flags
+// of rs_product_fwd (inner != 0, W != null), W the RAW [k, P, k] tensor.
+static int product_train_check(const char* what, const float* z, int64_t z_stride, const float* dx,
+                               int64_t dx_stride, int n_fields, int k, int inner, bool outer, int64_t batch) {
+  RS_REQUIRE(batch >= 0, "%s: negative batch", what);
+  RS_REQUIRE(z && dx, "%s: null pointer", what);
+  RS_REQUIRE(n_fields >= 2 && n_fields <= 128 && k >= 1 && k <= 16, "%s: need 2..128 fields and 1 <= k <= 16", what);
+  const int64_t fk = (int64_t)n_fields * k, P = (int64_t)n_fields * (n_fields - 1) / 2;
+  RS_REQUIRE(z_stride >= fk, "%s: z stride < F*k", what);
+  RS_REQUIRE(dx_stride >= fk + (inner ? P : 0) + (outer ? P : 0), "%s: gradient row stride too small", what);
+  return RS_OK;
+}
+
+extern "C" int rs_product_bwd(const float* z, int64_t z_stride, const float* dx, int64_t dx_stride, int n_fields,
+                              int k, int inner, const float* W, int64_t batch, float* dz, int64_t dz_stride,
+                              rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  RS_REQUIRE(dz, "rs_product_bwd: null pointer");
+  RS_REQUIRE(inner || W, "rs_product_bwd: nothing to compute (inner=0, no outer weights)");
+  if (int rc = product_train_check("rs_product_bwd", z, z_stride, dx, dx_stride, n_fields, k, inner, W != nullptr,
+                                   batch))
+    return rc;
+  const int64_t fk = (int64_t)n_fields * k, P = (int64_t)n_fields * (n_fields - 1) / 2;
+  RS_REQUIRE(dz_stride >= fk, "rs_product_bwd: dz stride < F*k");
+  ProdBwd a{};
+  a.z = z;
+  a.ldz = z_stride;
+  a.dx = dx;
+  a.ldx = dx_stride;
+  a.oi = inner ? fk : -1;
+  a.oo = W ? fk + (inner ? P : 0) : -1;
+  a.W = W;
+  a.F = n_fields;
+  a.k = k;
+  a.S = 16;
+  while (a.S > 1 && (size_t)a.S * (fk + 1) * sizeof(float) > 64 * 1024) a.S >>= 1;  // 16, 8 or 4 samples
+  a.B = batch;
+  a.dz = dz;
+  a.lddz = dz_stride;
+  launch_lds<product_bwd_kernel>((unsigned)((batch + a.S - 1) / a.S), 1024, (size_t)a.S * (fk + 1) * sizeof(float),
+                                 as_stream(stream), a);
+  return launch_status("rs_product_bwd");
+}
+
+extern "C" int rs_product_w_grad(const float* z, int64_t z_stride, const float* dx, int64_t dx_stride, int n_fields,
+                                 int k, int inner, int64_t batch, float* dW, rs_stream_t stream) {
+  if (int rc = product_train_check("rs_product_w_grad", z, z_stride, dx, dx_stride, n_fields, k, inner, true, batch))
+    return rc;
+  RS_REQUIRE(dW, "rs_product_w_grad: null pointer");
+  if (batch == 0) return RS_OK;  // (dW untouched, as rs_outer_product_w_grad)
+  const int64_t fk = (int64_t)n_fields * k, P = (int64_t)n_fields * (n_fields - 1) / 2;
+  outer_w_grad_kernel<<<(unsigned)P, 256, 0, as_stream(stream)>>>(z, z_stride, dx + fk + (inner ? P : 0), dx_stride,
+                                                                   n_fields, k, batch, dW);
+  return launch_status("rs_product_w_grad");
 }
 
 extern "C" int rs_bi_interaction_bwd(const float* emb, int64_t emb_stride, const float* dbi, int64_t dbi_stride,

@@ -261,9 +261,241 @@ static int fg_launch(const char* what, FgArgs& a, int id_kind, const int* filter
   return launch_status(what);
 }
 
+// ------------------------------------------------------------------ backward
+// The whole stack's backward in ONE launch (rs_fgcnn_conv_bwd).  A workgroup
+// takes samples b = blockIdx.x, + gridDim.x, ... one at a time and walks the
+// layers top down with four LDS regions: the layer's kernel, its zero-padded
+// input map X [H + kw - 1][k][Cin] (the rows for layer 0, the saved pooled map
+// of the layer below otherwise), its zero-padded gradient map dY
+// [H + kw - 1][k][Cout] (kw - 1 - pb rows in front, pb behind: the transposed
+// convolution's 'same' padding) and G [Hp][k][Cout], which carries a layer's
+// input gradient down to the next layer's pooled gradient.  Per layer:
+//   1. one thread per pooled value recomputes the pw members' conv sums (fp32
+//      chains in (t, c) order; the bias is common to the members), routes
+//      (dws + G) (1 - p^2) to the FIRST member that attains the maximum — p is
+//      the saved tanh(max + b) — and leaves every other dY entry zero;
+//   2. db[n] = sum dY, dW[t,c,n] = sum_{h,d} X[h+t,d,c] dY[h,d,n]: one thread
+//      per element, added into the workgroup's own partial row (the same
+//      thread owns the element for every sample: no atomics);
+//   3. dX[h,d,c] = sum_{t,n} dY[h - t + pb,d,n] W[t,c,n] into G, or for layer 0
+//      added into the caller's de.
+// fgcnn_bwd_finish then sums the partial rows in a fixed order.
+constexpr int FG_BWD_GRID = 512;  // workgroups (= partial rows) at most
+
+struct FgBwdArgs {
+  const float* z;
+  int64_t z_stride;
+  const float* ws;
+  int64_t ws_stride;
+  const float* dws;
+  int64_t dws_stride;
+  float* de;
+  int64_t de_stride;
+  float* part;  // [gridDim.x][gtot]: per layer dW then db
+  int k, L;
+  int xoff, yoff, goff;  // LDS regions after the kernel, floats
+  int gtot;
+  int64_t batch;
+  FgLayer l[FG_MAXL];
+  int g_off[FG_MAXL];  // the layer's first column of a partial row
+};
+
+__global__ __launch_bounds__(FG_NT) void fgcnn_conv_bwd(FgBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* wl = smem;
+  float* X = smem + a.xoff;
+  float* dY = smem + a.yoff;
+  float* G = smem + a.goff;
+  const int tid = threadIdx.x, k = a.k;
+  float* part = a.part + (int64_t)blockIdx.x * a.gtot;
+  bool first = true;
+  for (int64_t b = blockIdx.x; b < a.batch; b += gridDim.x, first = false) {
+    for (int li = a.L - 1; li >= 0; --li) {
+      const FgLayer& l = a.l[li];
+      const int Cin = l.Cin, Cout = l.Cout, kw = l.kw, pw = l.pw, H = l.H;
+      const int pb = (kw - 1) / 2, pf = kw - 1 - pb, HP = H + kw - 1;
+      const int nw = kw * Cin * Cout, nin = H * k * Cin, np = l.Hp * k * Cout;
+      __syncthreads();  // the layer above is done with wl, X and dY
+      for (int i = tid; i < nw; i += FG_NT) wl[i] = l.w[i];
+      for (int i = tid; i < HP * k * Cin; i += FG_NT) X[i] = 0.f;
+      for (int i = tid; i < HP * k * Cout; i += FG_NT) dY[i] = 0.f;
+      __syncthreads();
+      const float* src = li == 0 ? a.z + b * a.z_stride : a.ws + b * a.ws_stride + a.l[li - 1].ws_off;
+      for (int i = tid; i < nin; i += FG_NT) X[pb * k * Cin + i] = src[i];
+      __syncthreads();
+      // 1. the pool's winner takes the gradient
+      const float* pv = a.ws + b * a.ws_stride + l.ws_off;
+      const float* dv = a.dws + b * a.dws_stride + l.ws_off;
+      const bool top = li + 1 == a.L;
+      for (int i = tid; i < np; i += FG_NT) {
+        const int n = i % Cout, m = i / Cout, d = m % k, hp = m / k;
+        float best = 0.f;
+        int jb = 0;
+        for (int j = 0; j < pw; ++j) {
+          const float* xr = X + ((hp * pw + j) * k + d) * Cin;
+          float acc = 0.f;
+          for (int t = 0; t < kw; ++t)
+            for (int c = 0; c < Cin; ++c) acc = fmaf(xr[t * k * Cin + c], wl[(t * Cin + c) * Cout + n], acc);
+          if (j == 0 || acc > best) {
+            best = acc;
+            jb = j;
+          }
+        }
+        float g = dv[i];
+        if (!top) g += G[i];
+        const float p = pv[i];
+        dY[((pf + hp * pw + jb) * k + d) * Cout + n] = g * (1.f - p * p);
+      }
+      __syncthreads();
+      // 2. bias and kernel gradients into this workgroup's partial row
+      float* pr = part + a.g_off[li];
+      for (int n = tid; n < Cout; n += FG_NT) {
+        float s = 0.f;
+        for (int r = 0; r < H * k; ++r) s += dY[(pf * k + r) * Cout + n];
+        pr[nw + n] = first ? s : pr[nw + n] + s;
+      }
+      for (int e = tid; e < nw; e += FG_NT) {
+        const int n = e % Cout, tc = e / Cout, c = tc % Cin, t = tc / Cin;
+        const float* xr = X + t * k * Cin + c;
+        const float* yr = dY + pf * k * Cout + n;
+        float s = 0.f;
+        for (int r = 0; r < H * k; ++r) s = fmaf(xr[r * Cin], yr[r * Cout], s);
+        pr[e] = first ? s : pr[e] + s;
+      }
+      // 3. the transposed convolution
+      for (int i = tid; i < nin; i += FG_NT) {
+        const int c = i % Cin, m = i / Cin, d = m % k, h = m / k;
+        float s = 0.f;
+        for (int t = 0; t < kw; ++t) {
+          const float* yr = dY + ((h + kw - 1 - t) * k + d) * Cout;
+          const float* wr = wl + (t * Cin + c) * Cout;
+          for (int n = 0; n < Cout; ++n) s = fmaf(yr[n], wr[n], s);
+        }
+        if (li == 0) a.de[b * a.de_stride + i] += s;
+        else G[i] = s;
+      }
+    }
+  }
+}
+
+struct FgFinish {
+  float* dw[FG_MAXL];
+  float* db[FG_MAXL];
+  int g_off[FG_MAXL + 1];
+  int nw[FG_MAXL];
+  int L;
+};
+
+// column c of the partial rows summed in row order, four interleaved chains
+__global__ __launch_bounds__(256) void fgcnn_bwd_finish(const float* __restrict__ part, int rows, int gtot,
+                                                        FgFinish f) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= gtot) return;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int r = 0; r < rows; ++r) s[r & 3] += part[(int64_t)r * gtot + c];
+  const float v = (s[0] + s[1]) + (s[2] + s[3]);
+  int li = 0;
+  while (li + 1 < f.L && c >= f.g_off[li + 1]) ++li;
+  const int e = c - f.g_off[li];
+  if (e < f.nw[li]) f.dw[li][e] = v;
+  else f.db[li][e - f.nw[li]] = v;
+}
+
+// The backward's plan on top of fg_plan: LDS regions and the partial row's
+// layout.  Returns the LDS bytes, or -1 with the error string set.
+static int64_t fg_bwd_plan(const char* what, int F, int k, int L, const int* filters, const int* kw, const int* pw,
+                           FgBwdArgs* a) {
+  FgArgs fa{};
+  if (fg_plan(what, F, k, L, filters, kw, pw, &fa) < 0) return -1;
+  int64_t wmax = 0, xmax = 0, ymax = 0, gmax = 0, gtot = 0;
+  for (int i = 0; i < L; ++i) {
+    const FgLayer& l = fa.l[i];
+    const int64_t hp = l.H + l.kw - 1, nw = (int64_t)l.kw * l.Cin * l.Cout;
+    wmax = std::max(wmax, (nw + 3) / 4 * 4);
+    xmax = std::max(xmax, hp * k * l.Cin);
+    ymax = std::max(ymax, hp * k * l.Cout);
+    gmax = std::max(gmax, (int64_t)l.Hp * k * l.Cout);
+    a->l[i] = l;
+    a->g_off[i] = (int)gtot;
+    gtot += nw + l.Cout;
+  }
+  const int64_t lds = (wmax + xmax + ymax + gmax) * 4;
+  if (lds > FG_LDS_MAX) {
+    set_error("%s: the backward's per-sample LDS tile does not fit (%lld > %lld bytes)", what, (long long)lds,
+              (long long)FG_LDS_MAX);
+    return -1;
+  }
+  a->k = k;
+  a->L = L;
+  a->xoff = (int)wmax;
+  a->yoff = (int)(wmax + xmax);
+  a->goff = (int)(wmax + xmax + ymax);
+  a->gtot = (int)gtot;
+  return lds;
+}
+
 }  // namespace rs
 
 using namespace rs;
+
+extern "C" int64_t rs_fgcnn_conv_bwd_workspace_size(int n_fields, int k, int n_layers, const int* filters,
+                                                    const int* kernel_width, const int* pooling_width,
+                                                    int64_t batch) {
+  FgBwdArgs a{};
+  if (batch < 0) {
+    set_error("rs_fgcnn_conv_bwd_workspace_size: negative batch");
+    return -1;
+  }
+  if (fg_bwd_plan("rs_fgcnn_conv_bwd_workspace_size", n_fields, k, n_layers, filters, kernel_width, pooling_width,
+                  &a) < 0)
+    return -1;
+  return std::min<int64_t>(batch, FG_BWD_GRID) * a.gtot * 4;
+}
+
+extern "C" int rs_fgcnn_conv_bwd(const float* z, int64_t z_stride, const float* ws, int64_t ws_stride,
+                                 const float* dws, int64_t dws_stride, int n_fields, int k, int n_layers,
+                                 const int* filters, const int* kernel_width, const int* pooling_width,
+                                 const float* const* conv_w, float* de, int64_t de_stride, float* const* dconv_w,
+                                 float* const* dconv_b, void* workspace, int64_t workspace_bytes, int64_t batch,
+                                 rs_stream_t stream) {
+  if (batch == 0) return RS_OK;  // empty batch: nothing to launch (null data pointers allowed)
+  RS_REQUIRE(batch > 0, "rs_fgcnn_conv_bwd: negative batch");
+  RS_REQUIRE(z && ws && dws && de && conv_w && dconv_w && dconv_b && workspace, "rs_fgcnn_conv_bwd: null pointer");
+  FgBwdArgs a{};
+  const int64_t lds = fg_bwd_plan("rs_fgcnn_conv_bwd", n_fields, k, n_layers, filters, kernel_width, pooling_width, &a);
+  if (lds < 0) return RS_ERR_ARG;
+  const int64_t fk = (int64_t)n_fields * k, need = a.l[a.L - 1].ws_off + (int64_t)a.l[a.L - 1].Hp * k * a.l[a.L - 1].Cout;
+  RS_REQUIRE(z_stride >= fk && de_stride >= fk, "rs_fgcnn_conv_bwd: z / de stride < F*k");
+  RS_REQUIRE(ws_stride >= need && dws_stride >= need, "rs_fgcnn_conv_bwd: workspace stride < %lld", (long long)need);
+  const int64_t grid = std::min<int64_t>(batch, FG_BWD_GRID);
+  RS_REQUIRE(workspace_bytes >= grid * a.gtot * 4, "rs_fgcnn_conv_bwd: workspace of %lld bytes < %lld",
+             (long long)workspace_bytes, (long long)(grid * a.gtot * 4));
+  FgFinish f{};
+  f.L = a.L;
+  for (int i = 0; i < a.L; ++i) {
+    RS_REQUIRE(conv_w[i] && dconv_w[i] && dconv_b[i], "rs_fgcnn_conv_bwd: null weights (layer %d)", i);
+    a.l[i].w = conv_w[i];
+    f.dw[i] = dconv_w[i];
+    f.db[i] = dconv_b[i];
+    f.g_off[i] = a.g_off[i];
+    f.nw[i] = a.l[i].kw * a.l[i].Cin * a.l[i].Cout;
+  }
+  f.g_off[a.L] = a.gtot;
+  a.z = z;
+  a.z_stride = z_stride;
+  a.ws = ws;
+  a.ws_stride = ws_stride;
+  a.dws = dws;
+  a.dws_stride = dws_stride;
+  a.de = de;
+  a.de_stride = de_stride;
+  a.part = static_cast<float*>(workspace);
+  a.batch = batch;
+  hipStream_t st = as_stream(stream);
+  launch_lds<fgcnn_conv_bwd>((unsigned)grid, FG_NT, (size_t)lds, st, a);
+  fgcnn_bwd_finish<<<(unsigned)((a.gtot + 255) / 256), 256, 0, st>>>(a.part, (int)grid, a.gtot, f);
+  return launch_status("rs_fgcnn_conv_bwd");
+}
 
 extern "C" int64_t rs_fgcnn_workspace_size(int n_fields, int k, int n_layers, const int* filters,
                                            const int* kernel_width, const int* pooling_width) {

@@ -555,6 +555,50 @@ class FGCNNLayer(KerasModule):
         out = torch.empty(e.shape[0], self.n_new * self.k, dtype=torch.float32, device=self._dev)
         return self.recombine(ws, out).view(e.shape[0], self.n_new, self.k)
 
+    def bwd_workspace_size(self, B):
+        """Bytes of rs_fgcnn_conv_bwd's workspace at batch B; raises RSError
+        where the backward's per-sample tile does not fit in LDS."""
+        n = _lib.lib().rs_fgcnn_conv_bwd_workspace_size(self.field_num, self.k, *self._cfg(), int(B))
+        if n < 0:
+            _lib.check(-1, "rs_fgcnn_conv_bwd_workspace_size")
+        return int(n)
+
+    def backward(self, rows, ws, new, dnew, de):
+        """The layer's backward from dnew = dL/d(output) [B, n_new*k].  ``rows``
+        [B, >= F*k] holds the input rows in its first F*k columns, ``ws`` is the
+        forward's workspace and ``new`` its output (after the relu); all three
+        may be column views.  Per layer the recombination Dense: dpre = dnew
+        [new > 0], dkernel = ws_i^T dpre (rs_gemm), dbias (rs_col_sum), dws_i =
+        dpre kernel^T (rs_gemm into its columns of dws); then ONE
+        rs_fgcnn_conv_bwd launch ADDS dL/d(rows) into de [B, F*k] and writes
+        the conv kernels' and biases' gradients.  Returns {name: gradient},
+        keyed like keras_weights()."""
+        B, st = rows.shape[0], _stream()
+        emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self._dev)
+        grads = {}
+        dws = emp(B, self.ws_size)
+        shapes = [(*d.kernel.shape, B) for d in self.dense_layers] + [(B, *d.kernel.shape) for d in self.dense_layers]
+        gw = _train_ops.gemm_ws(self, _train_ops.gemm_need(shapes))
+        off = col = 0
+        for i, ((H, k, cout), d) in enumerate(zip(self.pooled_shapes, self.dense_layers)):
+            n, u = H * k * cout, d.units
+            dpre = dnew[:, col:col + u] * (new[:, col:col + u] > 0)
+            dW, db, _ = _train_ops.dense_backward(d.kernel, ws[:, off:off + n], dpre, gw, emp, st, d_in=False)
+            grads[f"dense_{i}/kernel"], grads[f"dense_{i}/bias"] = dW, db
+            call("rs_gemm", 0, 1, B, n, u, 1.0, ptr(dpre), u, ptr(d.kernel), u, 0.0, dws.data_ptr() + 4 * off,
+                 self.ws_size, None, 0, *gw, st)
+            off += n
+            col += u
+        dcw = [emp(*w.shape) for w in self.conv_kernels]
+        dcb = [emp(*b.shape) for b in self.conv_biases]
+        cws = scratch(self, "_bwd_ws", max(self.bwd_workspace_size(B), 1))
+        call("rs_fgcnn_conv_bwd", ptr(rows), rows.stride(0), ptr(ws), ws.stride(0), ptr(dws), dws.stride(0),
+             self.field_num, self.k, *self._cfg(), ptrs(self.conv_kernels), ptr(de), de.stride(0), ptrs(dcw), ptrs(dcb),
+             ptr(cws), cws.numel(), B, st)
+        for i in range(len(dcw)):
+            grads[f"conv_{i}/kernel"], grads[f"conv_{i}/bias"] = dcw[i], dcb[i]
+        return grads
+
 
 # -------------------------------------------------------------- dense / MLP
 _MLP_MAXL, _MLP_MAXD = 8, 1024  # rs_mlp_fwd limits (mlp.hip)

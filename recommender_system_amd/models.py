@@ -37,8 +37,9 @@ uses k=8 (layer/core.py:268-271), so 8 is the drop-in behaviour.
 PNN runs with 3-D embeddings [B,F,k] (documented deviation: the reference's
 rank-2 EmbedLayer makes PNN.call raise at model/pnn.py:38).  Modes 'inner',
 'outer' and 'both' are built (forward and training); an unknown mode raises
-the reference's ValueError.  use_fgcnn=True (forward only, HIP device only:
-building it for another device raises NotImplementedError) runs the product
+the reference's ValueError.  use_fgcnn=True (HIP device only: building it for
+another device raises NotImplementedError; trained only when built with
+``train_fgcnn=True``, see PNN) runs the product
 layers and the flat part on z = concat([embed, FGCNNLayer(embed)], axis=1)
 (model/pnn.py:33-48); extra keyword ``fgcnn`` passes FGCNNLayer's arguments.
 """
@@ -488,14 +489,31 @@ class PNN(KerasModule):
     FGCNNLayer(embed)], axis=1) (model/pnn.py:33-36) — the conv stack from the
     ids (which also gathers embed into z), one Dense per FGCNN layer into z,
     then rs_product_fwd on z; ``fgcnn`` (a dict) passes FGCNNLayer's
-    arguments.  Returns the DNN logit (no sigmoid, as the reference)."""
+    arguments.  Returns the DNN logit (no sigmoid, as the reference).
+
+    ``train_fgcnn`` (default False; True needs use_fgcnn=True, else
+    ValueError): with the default a use_fgcnn model refuses ``train_step`` /
+    ``gradients`` (NotImplementedError).  Training it is an opt-in because it
+    is a deviation: the reference builds FGCNN's recombination Dense layers
+    inside ``call`` (layer/interaction.py:253), so in its loop (model/pnn.py:
+    74-81) they are redrawn on every call and are not in model.variables —
+    the literal step never trains them and is not reproducible.  The forward
+    here already builds them once; train_fgcnn=True extends that to training:
+    conv kernels and biases, recombination kernels and biases, the DNN, the
+    outer-product W and the looked-up table rows all take the SGD step.
+    Limits: n_z <= 128 fields, k in {4, 8, 16}, and the conv backward's LDS
+    tile (rs_fgcnn_conv_bwd_workspace_size); anything else raises
+    NotImplementedError before any launch."""
 
     def __init__(self, feature_columns, mode, hidden_units, output_dim, activation="relu", dropout=0.2,
-                 use_fgcnn=False, embed_dim=8, device=None, seed=None, fgcnn=None):
+                 use_fgcnn=False, embed_dim=8, device=None, seed=None, fgcnn=None, train_fgcnn=False):
         super().__init__(device, seed)
         if mode not in ("inner", "outer", "both"):
             raise ValueError("Please choice mode's value in 'inner', 'outer', 'both'.")
         self.use_fgcnn = bool(use_fgcnn)
+        self.train_fgcnn = bool(train_fgcnn)
+        if self.train_fgcnn and not self.use_fgcnn:
+            raise ValueError("PNN train_fgcnn=True needs use_fgcnn=True")
         if self.use_fgcnn and self._dev.type != "cuda":
             # FGCNN exists only as HIP kernels; a model built for another device
             # could never run it, so it is refused when it is built
@@ -522,8 +540,10 @@ class PNN(KerasModule):
         self.dnn_layer.build(self.width)
         self._err = _ErrFlag(self._dev)
 
-    def product_inputs(self, inputs, check_ids=True):
-        """[flat_emb | inner | outer] (model/pnn.py:37-48) in one launch."""
+    def product_inputs(self, inputs, check_ids=True, keep=None):
+        """[flat_emb | inner | outer] (model/pnn.py:37-48) in one launch.
+        ``keep`` (a dict, use_fgcnn only) receives what the backward reads: z
+        and the conv stack's workspace ws."""
         _, ids = _split_criteo(inputs, self.nd, self._dev)
         e = self.embed_layer
         B = ids.shape[0]
@@ -541,6 +561,8 @@ class PNN(KerasModule):
                  out.stride(0), B, _lib.stream())
             if check_ids:
                 self._err.check("PNN")
+            if keep is not None:
+                keep["z"], keep["ws"] = z, ws
             return out
         hoff, hvoc = e.host_meta()  # field metadata also by value (the kernel-argument front end)
         if self.mode == "inner":
@@ -576,49 +598,114 @@ class PNN(KerasModule):
           regulariser (OuterProductLayer's l2 sits in model.losses, never
           added there).  The loop calls model(X) without training=True, so
           Dropout is the identity there too.  Returns the per-sample losses
-          (before the step) if ``return_loss``."""
+          (before the step) if ``return_loss``.
+
+        use_fgcnn=True trains only a model built with ``train_fgcnn=True``
+        (see the class docstring); then ``gradients`` also runs
+        rs_product_bwd / rs_product_w_grad on z and FGCNNLayer.backward, and
+        the conv kernels and biases and the recombination kernels and biases
+        take the same SGD step.  A bad id raises before any weight moves."""
+        grads, loss, ids = self._gradients(inputs, labels, check_ids, return_loss, "train_step")
+        names = dict(self.named_parameters())
+        de = grads.pop("embed_rows")
+        if ids.shape[0] == 0 and self.use_fgcnn:
+            return loss
+        st = _lib.stream()
+        _lib.sgd_update_multi([(names[n], g, g.numel(), 0.0) for n, g in grads.items()], lr, st)
+        embedding_sgd(self.embed_layer, ids, ptr(de), de.stride(0), lr, st, self)
+        self._weights_changed()
+        return loss
+
+    def gradients(self, inputs, labels, check_ids=True):
+        """The gradients of one ``train_step``'s loss, with no weight changed:
+        ({name: gradient} keyed like ``named_parameters()`` for every dense
+        tensor, plus "embed_rows": dL/d(looked-up rows) [B, F, k] per sample,
+        before the scatter into the table; the per-sample losses [B])."""
+        grads, loss, _ = self._gradients(inputs, labels, check_ids, True, "gradients")
+        e = self.embed_layer
+        grads["embed_rows"] = grads["embed_rows"].view(-1, e.n_fields, e.k)
+        return grads, loss
+
+    def _check_train(self, what):
         dnn = self.dnn_layer
-        if self.use_fgcnn:
-            raise NotImplementedError("PNN.train_step: use_fgcnn")
+        if self.use_fgcnn and not self.train_fgcnn:
+            raise NotImplementedError(f"PNN.{what}: use_fgcnn trains only a model built with train_fgcnn=True")
         if dnn.output_layer.units != 1:
-            raise NotImplementedError("PNN.train_step: output_dim 1 only")
+            raise NotImplementedError(f"PNN.{what}: output_dim 1 only")
         _check_train_tower("PNN", dnn)
+        if self.use_fgcnn:
+            if self.n_z > 128 or self.embed_layer.k not in (4, 8, 16):
+                raise NotImplementedError(f"PNN.{what}: use_fgcnn trains up to 128 fields of z (got {self.n_z}) "
+                                          f"and k in {{4, 8, 16}} (got {self.embed_layer.k})")
+            try:
+                self.fgcnn_layer.bwd_workspace_size(1)
+            except _lib.RSError as err:
+                raise NotImplementedError(f"PNN.{what}: {err}") from None
+
+    def _gradients(self, inputs, labels, check_ids, want_loss, what):
+        """({parameter name: gradient, "embed_rows": [B, F*k]}, losses or None,
+        ids) — the launches of one step up to, not including, the updates."""
+        self._check_train(what)
+        dnn = self.dnn_layer
         _, ids = _split_criteo(inputs, self.nd, self._dev)
         labels = _to_device_f32(labels, self._dev).reshape(-1)
         e = self.embed_layer
         B, F, k, st = ids.shape[0], e.n_fields, e.k, _lib.stream()
         emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self._dev)
-        x = self.product_inputs(inputs, check_ids)  # [B, F*k + P]: [flat | inner]
+        name_of = {id(p): n for n, p in self.named_parameters()}
+        if self.use_fgcnn and B == 0:  # nothing to launch: zero gradients, no losses
+            grads = {n: torch.zeros_like(p) for n, p in self.named_parameters() if p is not e.table}
+            grads["embed_rows"] = emp(0, F * k)
+            return grads, emp(0) if want_loss else None, ids
+        keep = {} if self.use_fgcnn else None
+        x = self.product_inputs(inputs, check_ids, keep=keep)  # [B, width]: [flat | inner | outer]
         layers = list(dnn.hidden_layer) + [dnn.output_layer]
         acts, _ = _dnn_train_forward(self, dnn, x, 0.0, st)  # (rate 0: no draw, as the loop)
         pre = dnn.output_layer(acts[-1])
         g = emp(B)
-        loss = emp(B) if return_loss else None
+        loss = emp(B) if want_loss else None
         call("rs_bce_prob_grad", ptr(pre), pre.stride(0), ptr(labels), B, ptr(g), ptr(loss), st)
         gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in layers]))
-        grads, delta = _dnn_backward(layers, acts, g.view(B, 1), gw, emp, st)
+        dgrads, delta = _dnn_backward(layers, acts, g.view(B, 1), gw, emp, st)
+        grads = {}
+        for L, dW, db in dgrads:
+            grads[name_of[id(L.kernel)]], grads[name_of[id(L.bias)]] = dW, db
         w = self.width
-        P = F * (F - 1) // 2
+        op = self.outer_product_layer
+        outer, inner = self.mode != "inner", self.mode != "outer"
         de = emp(B, F * k)
-        if self.mode in ("inner", "both"):
+        if self.use_fgcnn:
+            # dz [B, n_z*k] of [flat | inner | outer] in one launch; its new-field
+            # columns go back through FGCNNLayer, whose dL/d(rows) joins the first F*k
+            z, nz = keep["z"], self.n_z
+            dz = emp(B, nz * k)
+            call("rs_product_bwd", ptr(z), z.stride(0), ptr(delta), w, nz, k, 1 if inner else 0,
+                 ptr(op.W) if outer else None, B, ptr(dz), dz.stride(0), st)
+            if outer:
+                dW = emp(*op.W.shape)
+                call("rs_product_w_grad", ptr(z), z.stride(0), ptr(delta), w, nz, k, 1 if inner else 0, B, ptr(dW), st)
+                grads[name_of[id(op.W)]] = dW
+            de.copy_(dz[:, :F * k])
+            fg = self.fgcnn_layer
+            fgrads = fg.backward(z, keep["ws"], z[:, F * k:], dz[:, F * k:], de)
+            for n, p in fg.keras_weights().items():
+                grads[name_of[id(p)]] = fgrads[n]
+            grads["embed_rows"] = de
+            return grads, loss, ids
+        P = F * (F - 1) // 2
+        if inner:
             call("rs_inner_product_bwd", ptr(x), w, ptr(delta) + 4 * F * k, w, ptr(delta), w, F, k, B, ptr(de),
                  F * k, st)
         else:
             de.copy_(delta[:, :F * k])
-        dW = None
-        if self.mode in ("outer", "both"):
-            op = self.outer_product_layer
+        if outer:
             o0 = F * k + (P if self.mode == "both" else 0)  # the outer block's first column
             dW = emp(*op.W.shape)
             call("rs_outer_product_bwd", ptr(x), w, ptr(delta) + 4 * o0, w, ptr(op.W), F, k, B, ptr(de), F * k, st)
             call("rs_outer_product_w_grad", ptr(x), w, ptr(delta) + 4 * o0, w, F, k, B, ptr(dW), st)
-        upd = _dnn_updates(grads)
-        if dW is not None:
-            upd.append((self.outer_product_layer.W, dW, dW.numel(), 0.0))
-        _lib.sgd_update_multi(upd, lr, st)
-        embedding_sgd(e, ids, ptr(de), F * k, lr, st, self)
-        self._weights_changed()
-        return loss
+            grads[name_of[id(op.W)]] = dW
+        grads["embed_rows"] = de
+        return grads, loss, ids
 
 
 class DIN(TowerMixin, KerasModule):
