@@ -2129,6 +2129,83 @@ int rs_rows_fm_fwd(const float* emb, const float* dense, int64_t dense_stride,
                    const float* w0, int kfm, float* logit, int64_t batch,
                    rs_stream_t stream);
 
+/* ---- FNN (model/fnn.py:13-67): sigmoid(DNNLayer(x (.) v)) on the compact
+ * batch (dense [B, nd], ids [B, F], field_offsets / field_vocab as
+ * rs_fm_onehot_fwd), without the dense [B, n*k] input.  Sample b has A = nd +
+ * F active features: dense feature j is row j with value dense[b, j], field
+ * c is row nd + field_offsets[c] + id(b, c) with value 1.  With the first
+ * Dense kernel W1 [n*k, H1] viewed as [n, k, H1] (model/fnn.py:53-57),
+ *   z1[b, :] = b1 + sum_a x_a * (v[f_a, :] @ W1[f_a]).
+ * An id outside [0, vocab) (or a row past n_rows) sets RS_FLAG_BAD_ID and
+ * contributes nothing.  Every offset into W1 / P is int64.  No allocation,
+ * no synchronisation: stream-ordered and graph-capturable.
+ *
+ * rs_fnn_project: P[f, :] = v[f, :] @ W1[f] ([n_rows, H1]; j in order), one
+ *  streaming pass over W1 — the inference weight image.
+ * rs_fnn_first_layer_fwd: out[b, :] = act(b1 + sum_a x_a P[f_a]) ([B, H1],
+ *  rows out_stride apart; act RS_ACT_NONE / RELU / SIGMOID), dense features
+ *  first and then the fields, in order.  Any H1.
+ * rs_fnn_ok: 1 when rs_fnn_fwd runs a DNN of n_layers Dense layers (the
+ *  gathered first one included) with output widths dims[0 .. n_layers-1] and
+ *  activations acts[0 .. n_layers-1]: 2..9 layers, dims[n_layers-1] == 1,
+ *  RS_ACT_NONE / RELU / SIGMOID, and the fused tower's geometry (padded
+ *  widths <= 1024, LDS <= 160 KiB).
+ * rs_fnn_fwd: y[b] = sigmoid(DNN(x (.) v)) in one launch: a1 as
+ *  rs_fnn_first_layer_fwd computes it (bit-identical), staged in the input
+ *  tile of the fused tower, then layers 1.. from `prepared` = rs_mlp_prepare
+ *  of those layers (dims[0 .. n_layers-1]).  A shape rs_fnn_ok refuses is
+ *  RS_ERR_ARG and launches nothing.                                         */
+int rs_fnn_project(const float* v, const float* W1, int64_t n_rows, int k,
+                   int H1, float* P, rs_stream_t stream);
+int rs_fnn_first_layer_fwd(const void* ids, int id_kind, int64_t id_stride,
+                           const float* dense, int64_t dense_stride, int nd,
+                           const int64_t* field_offsets,
+                           const int64_t* field_vocab, int n_fields,
+                           const float* P, int64_t n_rows, int H1,
+                           const float* b1, int act, float* out,
+                           int64_t out_stride, int64_t batch, int* err_flag,
+                           rs_stream_t stream);
+int rs_fnn_ok(int n_layers, const int* dims, const int* acts);
+int rs_fnn_fwd(const void* ids, int id_kind, int64_t id_stride,
+               const float* dense, int64_t dense_stride, int nd,
+               const int64_t* field_offsets, const int64_t* field_vocab,
+               int n_fields, const float* P, int64_t n_rows, const float* b1,
+               int n_layers, const int* dims, const int* acts,
+               const float* prepared, float* y, int64_t y_stride,
+               int64_t batch, int* err_flag, rs_stream_t stream);
+
+/* FNN stage 2 (the second fit of model/fnn.py:56-63 trains the DNN only; v
+ * is a constant).  W1 moves every step, so there is no P: the B*A lookups
+ * are sorted once by row (stable radix sort) into `workspace`
+ * (rs_fnn_train_workspace_size bytes: O(B*A) + [U, H1] floats for U <=
+ * min(B*A, n_rows) distinct rows), and the sort serves both entries.
+ * rs_fnn_train_fwd: per distinct row Pu[u] = v[f_u] @ W1[f_u] (a touched
+ *  slab is read once however many samples share it), then out[b, :] =
+ *  act(b1 + sum_a x_a Pu[slot(b, a)]).
+ * rs_fnn_w1_sgd (same shape arguments and the workspace rs_fnn_train_fwd
+ *  left): dz1[b, c] = d_a1[b, c] * (mult ? mult[b, c] : 1) where mask is null
+ *  or mask[b, c] > 0, else 0 ([B, H1] contiguous; may alias d_a1 when
+ *  d_stride == H1); per distinct row g_f = sum over its lookups, in lookup
+ *  order, of x * dz1[b] (chunk pieces added in chunk order: no float
+ *  atomics, bit-identical run to run); g_out (optional) receives g_f by
+ *  ascending row, [U, H1]; W1 (optional) is updated in place, W1[f][j, :] -=
+ *  lr * v[f, j] * g_f — rows no sample touched are never written.          */
+int64_t rs_fnn_train_workspace_size(int64_t batch, int nd, int n_fields,
+                                    int64_t n_rows, int H1);
+int rs_fnn_train_fwd(const void* ids, int id_kind, int64_t id_stride,
+                     const float* dense, int64_t dense_stride, int nd,
+                     const int64_t* field_offsets, const int64_t* field_vocab,
+                     int n_fields, const float* v, const float* W1,
+                     int64_t n_rows, int k, int H1, const float* b1, int act,
+                     float* out, int64_t out_stride, int64_t batch,
+                     void* workspace, int* err_flag, rs_stream_t stream);
+int rs_fnn_w1_sgd(const float* d_a1, int64_t d_stride, const float* mult,
+                  int64_t mult_stride, const float* mask, int64_t mask_stride,
+                  const float* dense, int64_t dense_stride, int nd,
+                  int n_fields, const float* v, float* W1, int64_t n_rows,
+                  int k, int H1, int64_t batch, float lr, float* dz1,
+                  float* g_out, void* workspace, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

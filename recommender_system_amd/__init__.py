@@ -12,7 +12,7 @@ from .layers import (AFMLayer, Attention, AttentionLayer, BatchNormalization, Cr
                      OuterProductLayer, ResLayer, WideLayer, mmoe_layer, sigmoid_combine, tower_layer,
                      AUGRU, AUGRUCell, AttentionSequencePoolingLayer, DNN, GRU, InterestEvolution,
                      LocalActivationUnit, PredictionLayer, InBatchSoftmaxLayer, SequencePoolingLayer)
-from .models import AFM, DCN, DIEN, DIN, DSSM, FFM, FM, MMOE, NFM, PNN, DeepCrossing, DeepFM, WideDeep  # noqa: F401
+from .models import AFM, DCN, DIEN, DIN, DSSM, FFM, FM, FNN, MMOE, NFM, PNN, DeepCrossing, DeepFM, WideDeep  # noqa: F401
 from .feature_column import DenseFeat, SparseFeat, VarLenSparseFeat, get_feature_names  # noqa: F401
 from .negative import NegativeSampler, recall_N, sampledsoftmaxloss  # noqa: F401
 from .retrieval import topn_inner_product, topn_ok  # noqa: F401

@@ -232,6 +232,13 @@ SIGNATURES = {
     "rs_shard_row_route": (I, [P, I, L, P, P, I, L, L, I, P, I, P, P, P, P]),
     "rs_shard_owner_fm": (I, [P, L, I, I, P, L, I, I, I, P, I, P, L, L, P, P]),
     "rs_shard_fm_combine": (I, [P, L, I, L, P, L, I, I, I, P, P, I, P, P]),
+    "rs_fnn_project": (I, [P, P, L, I, I, P, P]),
+    "rs_fnn_first_layer_fwd": (I, [P, I, L, P, L, I, P, P, I, P, L, I, P, I, P, L, L, P, P]),
+    "rs_fnn_ok": (I, [I, P, P]),
+    "rs_fnn_fwd": (I, [P, I, L, P, L, I, P, P, I, P, L, P, I, P, P, P, P, L, L, P, P]),
+    "rs_fnn_train_workspace_size": (L, [L, I, I, L, I]),
+    "rs_fnn_train_fwd": (I, [P, I, L, P, L, I, P, P, I, P, P, L, I, I, P, I, P, L, L, P, P, P]),
+    "rs_fnn_w1_sgd": (I, [P, L, P, L, P, L, P, L, I, I, P, P, L, I, I, L, F, P, P, P, P]),
     "rs_shard_fm_pipe": (I, [P, I, I, P, L, P, L, P, P, I, L, P, P, L, P, I, P, I, L, I, I, I, P, P, I, P, P]),
     "rs_shard_fm_pipe_peer": (I, [P, P, P, I, I, I, I, P, L, P, L, P, P, I, L, P, P, L, P, I, I, L, I, I, I, P, P, I,
                                   P, P, I, P, I, L, P, P]),

@@ -19,6 +19,7 @@ models (Hcyand/recommender_system, algorithm/deep_learning/model/):
   FFM(feature_columns, k, w_reg=1e-4, v_reg=1e-4)                 model/ffm.py:10-22
   DeepCrossing(feature_columns, k, hidden_units, res_layer_num)   model/deepCrossing.py:15-32
   WideDeep(feature_columns, hidden_units, output_dim, activation) model/wideDeep.py:14-34
+  FNN(k, hidden_units, output_dim=1, activation='relu', w_reg, v_reg)  model/fnn.py:13-67
   MMOE(mmoe_hidden_units, num_experts, num_tasks, tower_hidden_units, output_dim,
        activation='relu', use_expert_bias=True, use_gate_bias=True) model/mmoe.py:10-32
   DIEN(dnn_feature_columns, history_feature_list, gru_type='GRU', ...)
@@ -1734,6 +1735,334 @@ class WideDeep(KerasModule):
             return ups
 
         return self._train(wide, wide_update, ids, labels, lr, return_loss, check_ids, dropout)
+
+
+class _FnnRest(TowerMixin, KerasModule):
+    """Layers 2..L + the output Dense of FNN's DNNLayer as a tower of their
+    own (their rs_mlp_prepare image: the first layer is the gather)."""
+
+    def __init__(self, dnn):
+        super().__init__(dnn._dev)
+        self.__dict__["_dnn"] = dnn  # not a submodule: the DNNLayer owns the weights
+
+    def _layers(self):
+        return self._dnn._layers()[1:]
+
+    def tower_ok(self):
+        return bool(self._layers()) and super().tower_ok()
+
+
+class FNN(KerasModule):
+    """FNN(k, hidden_units, output_dim=1, activation='relu', w_reg=1e-4,
+    v_reg=1e-4, dropout=0.2) — the two models of model/fnn.py:13-32 in one
+    class: ``self.fm = FM(k, w_reg, v_reg)`` and ``self.dnn =
+    DNNLayer(hidden_units, output_dim, activation)`` on x (.) v reshaped to
+    [B, n*k] (model/fnn.py:51-57), closed by a sigmoid.  (The reference's
+    class name DNN is DIEN's DNN layer here.)
+
+    The dense [B, n*k] input is never formed on the compact path: with the
+    first Dense kernel W1 (n*k, H1) viewed as [n, k, H1], z1 = b1 + sum over
+    a sample's nd + F active features of x_a * (v[f_a] @ W1[f_a]).
+    ``forward_onehot(dense, ids, field_offsets, field_vocab)`` gathers rows of
+    the projected table P[f] = v[f] @ W1[f] (rs_fnn_project, cached until a
+    weight moves) — in one launch with the rest of the tower where
+    ``fused_ok()`` (rs_fnn_fwd), else rs_fnn_first_layer_fwd + the tower
+    (``forward_unfused``).  ``forward(X)`` takes the literal one-hot matrix
+    [B, n] and forms x (.) v as the reference does (small n only).
+
+    Training follows the script: ``train_step_fm`` is FM.train_step (stage 1),
+    ``train_step`` one SGD step of the DNN on the constant x (.) v (stage 2;
+    v, w0, w1 get no gradient), ``fit`` both stages.  The model builds lazily
+    from nd + sum(field_vocab), as FM does."""
+
+    def __init__(self, k, hidden_units, output_dim=1, activation="relu", w_reg=1e-4, v_reg=1e-4, dropout=0.2,
+                 device=None, seed=None):
+        super().__init__(device, seed)
+        self.k = int(k)
+        self.output_dim = int(output_dim)
+        self.fm = FM(k, w_reg, v_reg, device=device, seed=_subseed(self._gen))
+        self.dnn = DNNLayer(list(hidden_units), output_dim, activation, dropout, device=device,
+                            seed=_subseed(self._gen))
+        self._rest = _FnnRest(self.dnn)
+
+    # ---- weights
+    @property
+    def built(self):
+        return self.fm.fm.built and self.dnn._layers()[0].kernel is not None
+
+    def build(self, n):
+        """Build both models for n = nd + sum(field_vocab) one-hot columns."""
+        if not self.fm.fm.built:
+            self.fm.fm.build(int(n))
+        if self.dnn._layers()[0].kernel is None:
+            self.dnn.build(int(n) * self.k)
+        self._weights_changed()
+
+    def keras_weights(self):
+        out = _prefixed("fm", self.fm.fm.keras_weights())
+        out.update(_prefixed("dnn", self.dnn.keras_weights()))
+        return out
+
+    def set_keras_weights(self, weights, strict=True):
+        if not self.built and "fm/v" in weights:
+            self.build(torch.as_tensor(weights["fm/v"]).shape[0])
+        if strict:
+            unknown = set(weights) - set(self.keras_weights())
+            if unknown:
+                raise KeyError(f"unknown weights {sorted(unknown)}")
+        _set_prefixed(self.fm.fm, "fm", weights, strict)
+        _set_prefixed(self.dnn, "dnn", weights, strict)
+        self._weights_changed()
+
+    def _batch(self, dense, ids, field_offsets, field_vocab):
+        """The compact batch on the device, checked: (dense [B, nd] f32, ids
+        [B, F], offsets int64 [F], vocab int64 [F]); builds the model."""
+        offs_h = torch.as_tensor(field_offsets, dtype=torch.int64).reshape(-1)
+        voc_h = torch.as_tensor(field_vocab, dtype=torch.int64).reshape(-1)
+        ids = _ids_tensor(ids, self._dev)
+        if ids.dim() == 2 and ids.stride(1) != 1:
+            ids = ids.contiguous()  # the kernels take a row stride only
+        if ids.dim() != 2 or offs_h.numel() != ids.shape[1] or voc_h.numel() != ids.shape[1]:
+            raise ValueError(f"FNN: ids {tuple(ids.shape)} need one field_offsets / field_vocab entry per column "
+                             f"(got {offs_h.numel()} / {voc_h.numel()})")
+        dense = _to_device_f32(dense, self._dev)
+        if dense.dim() != 2 or dense.shape[0] != ids.shape[0]:
+            raise ValueError(f"FNN: dense {tuple(dense.shape)} does not match ids {tuple(ids.shape)}")
+        n = dense.shape[1] + int(voc_h.cpu().sum())  # (a host sum: not inside a graph capture)
+        if not self.built:
+            self.build(n)
+        if n != self.fm.fm.v.shape[0]:
+            raise ValueError(f"FNN built for {self.fm.fm.v.shape[0]} one-hot columns, got {n}")
+        return dense, ids, offs_h.to(self._dev), voc_h.to(self._dev)
+
+    def projected(self):
+        """P [n, H1] = v[f] @ W1[f] (rs_fnn_project), cached on (v, W1)."""
+        v, W1 = self.fm.fm.v, self.dnn._layers()[0].kernel
+
+        def build():
+            P = torch.empty(v.shape[0], W1.shape[1], dtype=torch.float32, device=self._dev)
+            call("rs_fnn_project", ptr(v), ptr(W1), v.shape[0], self.k, W1.shape[1], ptr(P), _lib.stream())
+            return P
+        return self._packed("fnn_p", (v, W1), build)
+
+    # ---- inference
+    def fused_ok(self):
+        ls = self.dnn._layers()
+        if not self.built or self.output_dim != 1 or len(ls) < 2 or any(l.activation not in _lib.ACT for l in ls):
+            return False
+        return bool(_lib.lib().rs_fnn_ok(len(ls), ints([l.units for l in ls]),
+                                         ints([_lib.ACT[l.activation] for l in ls])))
+
+    def first_layer(self, dense, ids, field_offsets, field_vocab, check_ids=True, activate=True):
+        """a1 = act(z1) (z1 with ``activate=False``) [B, H1] of the first
+        Dense layer on x (.) v: rs_fnn_first_layer_fwd."""
+        dense, ids, offs, voc = self._batch(dense, ids, field_offsets, field_vocab)
+        first = self.dnn._layers()[0]
+        B, nd = dense.shape
+        out = torch.empty(B, first.units, dtype=torch.float32, device=self._dev)
+        P = self.projected()
+        err = _ErrFlag(self._dev)
+        call("rs_fnn_first_layer_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense), dense.stride(0), nd,
+             ptr(offs), ptr(voc), ids.shape[1], ptr(P), P.shape[0], first.units, ptr(first.bias),
+             _lib.ACT[first.activation if activate else None], ptr(out), out.stride(0), B, ptr(err.t), _lib.stream())
+        if check_ids:
+            err.check("FNN")
+        return out
+
+    def forward_unfused(self, dense, ids, field_offsets, field_vocab, check_ids=True):
+        """The composition: rs_fnn_first_layer_fwd, then layers 2..L + the
+        head as rs_mlp_fwd (layer by layer where the tower refuses them)."""
+        if any(l.activation not in _lib.ACT for l in self.dnn._layers()[:1]):
+            raise NotImplementedError("FNN: the first layer takes 'relu', 'sigmoid' or linear")
+        a = self.first_layer(dense, ids, field_offsets, field_vocab, check_ids)
+        rest = self._rest
+        if rest.tower_ok():
+            if self.output_dim == 1:
+                return rest.tower(a, head=True)
+            return sigmoid_combine(rest.tower(a))
+        for layer in rest._layers():
+            a = layer(a)
+        return sigmoid_combine(a)
+
+    def forward_fused(self, dense, ids, field_offsets, field_vocab, check_ids=True):
+        """ids -> a1 -> tower -> sigmoid in one launch (rs_fnn_fwd)."""
+        dense, ids, offs, voc = self._batch(dense, ids, field_offsets, field_vocab)
+        if not self.fused_ok():
+            raise ValueError("FNN.forward_fused: shape not supported (fused_ok() is False)")
+        ls = self.dnn._layers()
+        B, nd = dense.shape
+        y = torch.empty(B, 1, dtype=torch.float32, device=self._dev)
+        P = self.projected()
+        err = _ErrFlag(self._dev)
+        call("rs_fnn_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense), dense.stride(0), nd, ptr(offs),
+             ptr(voc), ids.shape[1], ptr(P), P.shape[0], ptr(ls[0].bias), len(ls), ints([l.units for l in ls]),
+             ints([_lib.ACT[l.activation] for l in ls]), ptr(self._rest.prepared()), ptr(y), 1, B, ptr(err.t),
+             _lib.stream())
+        if check_ids:
+            err.check("FNN")
+        return y
+
+    def forward_onehot(self, dense, ids, field_offsets, field_vocab, check_ids=True):
+        """sigmoid(DNN(x (.) v)) [B, output_dim] on the compact batch."""
+        if not self.built:
+            self._batch(dense, ids, field_offsets, field_vocab)
+        if self.fused_ok():
+            return self.forward_fused(dense, ids, field_offsets, field_vocab, check_ids)
+        return self.forward_unfused(dense, ids, field_offsets, field_vocab, check_ids)
+
+    def forward(self, X):
+        """The reference's formulation on the one-hot matrix X [B, n] (any
+        dense x): (X[:, :, None] * v) reshaped to [B, n*k] through the dense
+        tower (model/fnn.py:65-67).  Small n only: the input is B*n*k floats."""
+        X = _to_device_f32(X, self._dev)
+        B, n = X.shape
+        if not self.built:
+            self.build(n)
+        v = self.fm.fm.v
+        if n != v.shape[0]:
+            raise ValueError(f"FNN built for {v.shape[0]} one-hot columns, got {n}")
+        xv = (X[:, :, None] * v).reshape(B, n * self.k)
+        return sigmoid_combine(self.dnn(xv))
+
+    def fm_forward_onehot(self, dense, ids, field_offsets, field_vocab, check_ids=True):
+        """The FM's own prediction (``fm_pre`` of model/fnn.py:48)."""
+        return self.fm.forward_onehot(dense, ids, field_offsets, field_vocab, check_ids)
+
+    # ---- training
+    def train_step_fm(self, dense, ids, labels, field_offsets, field_vocab, lr=0.01, return_loss=False,
+                      check_ids=True):
+        """Stage 1: one FM.train_step (model/fnn.py:40-46).  v moves, so the
+        projected table is dropped."""
+        try:
+            return self.fm.train_step(dense, ids, labels, field_offsets, field_vocab, lr, return_loss, check_ids)
+        finally:
+            self._weights_changed()
+
+    def _check_train(self, what):
+        _check_train_tower("FNN", self.dnn)
+        if self.output_dim != 1:
+            raise NotImplementedError(f"{what}: output_dim 1 only")
+
+    def _stage2(self, what, dense, ids, labels, field_offsets, field_vocab, lr, want_loss, check_ids, dropout, update):
+        self._check_train(what)
+        dev = self._dev
+        dense, ids, offs, voc = self._batch(dense, ids, field_offsets, field_vocab)
+        if dev.type != "cuda":
+            raise _lib.RSError(f"{what}: librs_hip kernels need device (HIP) tensors; the model is on {dev}")
+        labels = _to_device_f32(labels, dev).reshape(-1)
+        B, nd = dense.shape
+        F = ids.shape[1]
+        layers = self.dnn._layers()
+        first, rest, hidden = layers[0], layers[1:], list(self.dnn.hidden_layer)
+        v, W1 = self.fm.fm.v, first.kernel
+        n, k, H1 = v.shape[0], self.k, first.units
+        rate = _dropout_rate(self.dnn, dropout) if hidden else 0.0
+        st = _lib.stream()
+        emp = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        size = _lib.lib().rs_fnn_train_workspace_size(B, nd, F, n, H1)
+        if size < 0:
+            _lib.check(-1, "rs_fnn_train_workspace_size")
+        ws = scratch(self, "_fnn_ws", size)
+        a1 = emp(B, H1)
+        err = _ErrFlag(dev)
+        call("rs_fnn_train_fwd", ptr(ids), _lib.id_kind(ids), ids.stride(0), ptr(dense), dense.stride(0), nd,
+             ptr(offs), ptr(voc), F, ptr(v), ptr(W1), n, k, H1, ptr(first.bias), _lib.ACT[first.activation], ptr(a1),
+             H1, B, ptr(ws), ptr(err.t), st)
+        if check_ids:
+            err.check(what)
+        # Dropout after every hidden layer, the first included; the first
+        # layer's multiplier is kept (the step's counter moves before dz1 is formed)
+        drop = mult = None
+        if rate > 0:
+            rng = _dropout_rng(self)
+            off0 = rng.draw(a1, rate, st)
+            mult = torch.ones(B, H1, dtype=torch.float32, device=dev)
+            rng.redraw(mult, rate, off0, st)
+            drop = (rng, rate, [off0])
+        acts = [a1]
+        for layer in hidden[1:]:
+            a = layer(acts[-1])
+            if drop is not None:
+                drop[2].append(drop[0].draw(a, rate, st))
+            acts.append(a)
+        logit = self.dnn.output_layer(acts[-1]) if rest else a1
+        g, loss = bce_head_logit(logit.reshape(-1), labels, want_loss, st)
+        if rest:
+            gw = gemm_ws(self, gemm_need([(*L.kernel.shape, B) for L in rest]))
+            sub = (drop[0], drop[1], drop[2][1:]) if drop is not None else None
+            grads, d_a1 = _dnn_backward(rest, acts, g.view(B, 1), gw, emp, st, drop=sub)
+        else:
+            grads, d_a1 = [], g.view(B, 1)
+        mask = a1 if first.activation == "relu" else None
+        dz1 = emp(B, H1)
+        g_rows = None if update else emp(min(B * (nd + F), n), H1)
+        call("rs_fnn_w1_sgd", ptr(d_a1), d_a1.stride(0), ptr(mult), H1, ptr(mask), H1, ptr(dense), dense.stride(0),
+             nd, F, ptr(v), ptr(W1) if update else None, n, k, H1, B, float(lr), ptr(dz1), ptr(g_rows), ptr(ws), st)
+        db1 = emp(H1)
+        call("rs_col_sum", ptr(dz1), H1, B, H1, ptr(db1), st)
+        if update:
+            _lib.sgd_update_multi(_dnn_updates(grads) + [(first.bias, db1, H1, 0.0)], lr, st)
+            self._weights_changed()
+            return loss
+        rows = torch.cat([torch.arange(nd, device=dev).expand(B, nd), nd + offs + ids.to(torch.int64)], dim=1)
+        valid = torch.cat([torch.ones(B, nd, dtype=torch.bool, device=dev),
+                           (ids.to(torch.int64) >= 0) & (ids.to(torch.int64) < voc)], dim=1)
+        rows = torch.unique(rows[valid])
+        g_rows = g_rows[:rows.numel()]
+        return {"rows": rows, "g": g_rows, "dW1": v[rows].unsqueeze(2) * g_rows.unsqueeze(1), "db1": db1,
+                "layers": [(dW, db) for _, dW, db in reversed(grads)], "loss": loss}
+
+    def train_step(self, dense, ids, labels, field_offsets, field_vocab, lr=1e-4, return_loss=False, check_ids=True,
+                   dropout=None):
+        """Stage 2: one step of the second fit of model/fnn.py:56-63 (SGD(lr),
+        binary cross-entropy on the sigmoid output, no regulariser) on a
+        compact batch.  Only the DNN trains: x (.) v is that fit's constant
+        input.  rs_fnn_train_fwd sorts the B*(nd+F) lookups by row once and
+        computes a1; Dropout(rate) follows every hidden layer, the first
+        included (``dropout=False`` turns it off, a float overrides the
+        rate); layers 2..L and the head go forward and backward as in every
+        other step; rs_fnn_w1_sgd turns dL/da1 into the row-sparse rank-1
+        update of W1 (a slab no sample touched is not written) and rs_col_sum
+        into db1.  'relu' / linear towers, output_dim 1.  Returns the
+        per-sample losses before the step if ``return_loss``."""
+        return self._stage2("FNN.train_step", dense, ids, labels, field_offsets, field_vocab, lr, return_loss,
+                            check_ids, dropout, True)
+
+    def gradients(self, dense, ids, labels, field_offsets, field_vocab, check_ids=True, dropout=False):
+        """What ``train_step`` would apply, without applying it: ``rows`` (the
+        distinct one-hot rows of the batch, ascending), ``g`` [U, H1] (g_f per
+        row), ``dW1`` [U, k, H1] (the touched slabs outer(v[f], g_f); every
+        other slab's gradient is zero), ``db1``, ``layers`` [(dW, db)] of
+        layers 2..L and the output Dense, and the per-sample ``loss``."""
+        return self._stage2("FNN.gradients", dense, ids, labels, field_offsets, field_vocab, 0.0, True, check_ids,
+                            dropout, False)
+
+    def fit(self, dense, ids, labels, field_offsets, field_vocab, batch_size=32, epochs_fm=20, lr_fm=0.01,
+            epochs_dnn=50, lr_dnn=1e-4, dropout=None):
+        """The two fits of model/fnn.py:40-63 on sequential batches (no
+        shuffle, as train.compile_fit): epochs_fm of the FM, then epochs_dnn
+        of the DNN on x (.) v with the trained v.  Returns {'fm': [...],
+        'dnn': [...]}: per epoch, the mean over the samples of the losses
+        taken before each batch's step."""
+        dense = _to_device_f32(dense, self._dev)
+        ids = _ids_tensor(ids, self._dev)
+        labels = _to_device_f32(labels, self._dev).reshape(-1)
+        N, bs = ids.shape[0], int(batch_size)
+        history = {"fm": [], "dnn": []}
+        for name, epochs in (("fm", epochs_fm), ("dnn", epochs_dnn)):
+            for _ in range(int(epochs)):
+                total = torch.zeros((), dtype=torch.float64, device=self._dev)
+                for b0 in range(0, N, bs):
+                    sl = slice(b0, min(b0 + bs, N))
+                    if name == "fm":
+                        loss = self.train_step_fm(dense[sl], ids[sl], labels[sl], field_offsets, field_vocab, lr_fm,
+                                                  return_loss=True)
+                    else:
+                        loss = self.train_step(dense[sl], ids[sl], labels[sl], field_offsets, field_vocab, lr_dnn,
+                                               return_loss=True, dropout=dropout)
+                    total += loss.double().sum()
+                history[name].append(float(total) / max(N, 1))
+        return history
 
 
 _MMOE_ACTS = ("relu", "sigmoid", "linear", None)  # what rs_mmoe_fwd's towers take (tower_layer's Dense has no alpha)
