@@ -2206,6 +2206,61 @@ int rs_fnn_w1_sgd(const float* d_a1, int64_t d_stride, const float* mult,
                   int k, int H1, int64_t batch, float lr, float* dz1,
                   float* g_out, void* workspace, rs_stream_t stream);
 
+/* ------------------------------------------------------ evaluation metrics
+ * What the reference's scripts print after training: accuracy_score(y_test,
+ * [p > 0.5]) (model/fm.py:38, deepFM.py:51, dcn.py:50, din.py:116, pnn.py:89,
+ * fnn.py:70-71; metrics=['accuracy'] in utils/compile_fit.py:13), plus the
+ * log-loss Keras reports and the ROC AUC two of the scripts name.  Stream-
+ * ordered, graph-capturable, no allocation, no synchronisation; n < 2^31 (the
+ * size queries answer -1 and the entries RS_ERR_ARG beyond, before any device
+ * work); n == 0 is allowed.
+ *
+ * rs_binary_metrics: pred [n] probabilities (pred_stride floats apart),
+ *  labels [n].  result: 8 words of 8 bytes —
+ *   0 n            int64
+ *   1 n_pos        int64   labels == 1
+ *   2 n_correct    int64   (p > 0.5) == (y == 1): Keras binary_accuracy
+ *   3 loss_sum     fp64    sum of -(y log(q + eps) + (1 - y) log(1 - q + eps)),
+ *                          q = clip(p, eps, 1 - eps), eps = 1e-7, every
+ *                          operand promoted to fp64 first (rs_bce_prob_grad's
+ *                          form without the fp32 log error)
+ *   4 n_bad_label  int64   labels that are neither 0.0 nor 1.0
+ *   5 n_nan_pred   int64   NaN predictions (they add nothing to loss_sum)
+ *   6, 7           reserved (0)
+ *  accumulate != 0 adds into result (which then must hold an earlier result
+ *  or zeros) instead of overwriting it.  Sums go workgroup partials -> one
+ *  workgroup, in a fixed order: bit-identical run to run.  workspace:
+ *  rs_binary_metrics_workspace_size(n) bytes.
+ *
+ * rs_auc: exact tie-aware ROC AUC of any finite fp32 scores (logits too);
+ *  -0.0 ties with +0.0, +-inf are the extremes.  A stable 32-bit radix sort of
+ *  (order-preserving key, sample), scans of the positives and of the tie-run
+ *  heads, and one thread per tie run adding p_r (2 below_r + n_r) into an
+ *  int64 (U2: twice the number of correctly ordered (positive, negative)
+ *  pairs, a tied pair counting half); auc = U2 / (2 P Q), NaN when P Q == 0.
+ *  group_ids non-null (group_kind RS_ID_I32 / RS_ID_I64, 0 <= id < n_groups;
+ *  any other id sets RS_FLAG_BAD_ID in word 6 and is read as group 0): also
+ *  gauc = sum_g size_g AUC_g / sum_g size_g over the groups that hold both
+ *  classes (impression-weighted, the DIN paper's), from a second stable sort
+ *  by group id.  result: 16 words of 8 bytes —
+ *   0 n  1 P  2 Q  3 U2            int64
+ *   4 auc                          fp64
+ *   5 n_nan_score  6 rs_flag bits  7 n_bad_label    int64
+ *   8 gauc                         fp64 (NaN without groups / no group used)
+ *   9 groups_used  10 impressions_used              int64
+ *   11..15                         reserved (0)
+ *  With n_nan_score or n_bad_label non-zero the other words mean nothing.
+ *  workspace: rs_auc_workspace_size(n, n_groups) bytes (n_groups = 0: no
+ *  group ids).  Integer atomics only: bit-identical run to run.            */
+int64_t rs_binary_metrics_workspace_size(int64_t n);
+int rs_binary_metrics(const float* pred, int64_t pred_stride,
+                      const float* labels, int64_t n, int accumulate,
+                      void* result, void* workspace, rs_stream_t stream);
+int64_t rs_auc_workspace_size(int64_t n, int64_t n_groups);
+int rs_auc(const float* scores, int64_t score_stride, const float* labels,
+           const void* group_ids, int group_kind, int64_t n_groups, int64_t n,
+           void* result, void* workspace, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,10 @@ SIGNATURES = {
     "rs_shard_fm_pipe": (I, [P, I, I, P, L, P, L, P, P, I, L, P, P, L, P, I, P, I, L, I, I, I, P, P, I, P, P]),
     "rs_shard_fm_pipe_peer": (I, [P, P, P, I, I, I, I, P, L, P, L, P, P, I, L, P, P, L, P, I, I, L, I, I, I, P, P, I,
                                   P, P, I, P, I, L, P, P]),
+    "rs_binary_metrics_workspace_size": (L, [L]),
+    "rs_binary_metrics": (I, [P, L, P, L, I, P, P, P]),
+    "rs_auc_workspace_size": (L, [L, L]),
+    "rs_auc": (I, [P, L, P, P, I, L, L, P, P, P]),
 }
 
 ID_I32, ID_I64, ID_F32 = 0, 1, 2
